@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DeepSDF shape/pose Gauss-Newton hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 5 --warmup 1 [--config cfg2x64|cfg4|cfg5] [--prepass auto|off|f16|bf16]
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--config cfg2x64|cfg4|cfg5] [--prepass auto|off|f16|bf16] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,11 @@ Workloads (BASELINE.json configs):
           distributed.shard_objects (--partition static | measured): "scaling": "strong"; --objects-per-gpu makes it a weak-scaling run;
   cfg5    4000-point objects, Redwood hyper-parameters (5 iterations), a mixed batch on two resident decoders (cars, 64-D codes +
           chairs32, 32-D codes and its own weights), 32 + 32 objects per GPU.
+
+--dump-outputs DIR writes what the last timed step of the headline run returned -- the result rows of every object of every rank, in
+object order, as Batch.results() hands them to a caller -- to DIR/t_cam_obj.npy (N, 4, 4), DIR/code.npy (N, 64; a 32-D code fills the first
+32 columns), DIR/loss.npy (N,) and DIR/status.npy (N,; 0 = good), all float32.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 The JSON line also carries
   roofline      fp32-MFMA roofline of the dominant fp32 kernel (forward decoder with relu-mask export, mlp_kernel<1>):
@@ -93,6 +98,28 @@ def reference_cpu_baseline(obj, threads):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, packed, D):
+    """Write the packed result rows (distributed.pack_results: n x 82 float32, every rank's objects in order) as the arrays a caller of the
+    batch receives.  Above DUMP_MAX_BYTES a fixed, seeded sample of the objects is kept and its indices go to object_index.npy."""
+    packed = np.asarray(packed, np.float32)
+    if packed.nbytes > DUMP_MAX_BYTES:
+        per_object = packed.itemsize * packed.shape[1] + 8        # its row + its float64 index
+        keep = np.sort(np.random.default_rng(0).choice(len(packed), DUMP_MAX_BYTES // per_object, replace=False))
+        packed = packed[keep]
+    else:
+        keep = None
+    os.makedirs(out_dir, exist_ok=True)
+    t, code, loss, status = D.unpack_results(packed)
+    arrays = {"t_cam_obj": t, "code": code, "loss": loss, "status": status}
+    if keep is not None:
+        arrays["object_index"] = keep.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,7 +135,10 @@ def main():
     ap.add_argument("--no-lp", action="store_true")              # skip the low-precision-compute sub-record (value_lp)
     ap.add_argument("--latency-runs", type=int, default=9)
     ap.add_argument("--serial-batches", action="store_true")     # cfg5: run the two decoders' batches back to back from one host thread (round 5's form)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)  # the last timed step's results as DIR/<name>.npy (module docstring)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -297,6 +327,8 @@ def main():
         return elapsed, per_rank, acc
 
     elapsed, per_rank_s, acc = timed(args.warmup, args.steps, "headline")
+    if args.dump_outputs and rank == 0:      # before the legs below overwrite `gathered`; outside every timed region
+        dump_outputs(args.dump_outputs, gathered[0], D)
     # the same batch with the prepass OFF, timed in the same run (every rank takes part: the steps contain the collective)
     off_run = None
     if args.config == "cfg2x64" and int(acc.get("prepass_mode", 0)) != 0 and not args.no_prepass_off:

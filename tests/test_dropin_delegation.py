@@ -11,9 +11,12 @@ mirror first on sys.path, the process's working directory = the DSP-SLAM source 
   * against the REAL reference checkout where there is one (/root/reference in the build container), with cv2 / mmcv / mmdet / mmdet3d
     stubbed in sys.modules (absent from this image; only module-level imports need them on the paths taken);
   * against a stand-in checkout written by the test (a `reconstruct/kitti_sequence.py` with the reference module's import lines), so the
-    mechanism is covered on a box without the reference too.
+    mechanism is covered on a box without the reference too;
+  * against tests/golden/golden_dropin.npz (tools/make_golden_dropin.py): what the reference's read_calib_file / load_velo_scan returned on
+    the files write_kitti_dir() writes, and every name its reference-only modules import from the modules the mirror serves.
 No GPU: get_decoder is left out here; tests/test_embed_harness.py makes the same get_sequence call from C++ after get_decoder.
 """
+import ast
 import json
 import os
 import subprocess
@@ -23,10 +26,11 @@ import textwrap
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, golden
+from oracle import ref_shim
 
 MIRROR = os.path.join(ROOT, "dsp_slam_amd")
-REFERENCE = "/root/reference"
+REFERENCE = ref_shim.REFERENCE_ROOT
 have_reference = os.path.isfile(os.path.join(REFERENCE, "reconstruct", "kitti_sequence.py"))
 
 STUBS = textwrap.dedent('''
@@ -234,8 +238,30 @@ def test_without_a_checkout_the_error_says_what_to_do(tmp_path):
     assert "DSP_REFERENCE_ROOT" in out["error"] and out["attr"] == "AttributeError"
 
 
+def test_mirror_serves_every_name_the_reference_only_modules_import(tmp_path):
+    """Every `from reconstruct... import name` of the reference's kitti_sequence / mono_sequence / detector2d / detector3d (recorded in
+    golden_dropin.npz) resolves in the mirror, and the stand-in checkout above imports exactly what the real kitti_sequence.py imports."""
+    imports = json.loads(str(golden("golden_dropin.npz")["imports_json"]))
+    assert sorted(imports) == ["detector2d", "detector3d", "kitti_sequence", "mono_sequence"]
+    wanted = sorted({(m, n) for per in imports.values() for m, names in per.items() for n in names})
+    assert wanted
+    out = run_as_system_cc(str(tmp_path), '''
+        import importlib
+        for m, n in %r:
+            print("%%s.%%s" %% (m, n), getattr(importlib.import_module(m), n).__module__)
+    ''' % (wanted,))
+    for m, n in wanted:
+        assert out["%s.%s" % (m, n)].split(".")[0] == "reconstruct", (m, n, out)
+    standin = {}
+    for node in ast.walk(ast.parse(textwrap.dedent(STANDIN))):
+        if isinstance(node, ast.ImportFrom) and node.module.split(".")[0] == "reconstruct":
+            standin.setdefault(node.module, []).extend(a.name for a in node.names)
+    assert {k: sorted(v) for k, v in standin.items()} == imports["kitti_sequence"]
+
+
 def test_read_calib_file_matches_the_reference(tmp_path):
-    """The mirror's two loader helpers against the reference's own functions on the same files (where a reference checkout exists)."""
+    """The mirror's two loader helpers against what the reference's own functions returned on the same files (golden_dropin.npz), and
+    against the live functions where a reference checkout exists."""
     d = str(tmp_path / "k")
     os.makedirs(d)
     write_kitti_dir(d)
@@ -252,8 +278,11 @@ def test_read_calib_file_matches_the_reference(tmp_path):
         sys.path.remove(MIRROR)
         for m in [k for k in sys.modules if k.split(".")[0] in ("reconstruct", "deep_sdf")]:
             del sys.modules[m]
+    g = golden("golden_dropin.npz")
+    recorded = {k[len("calib_"):]: g[k] for k in g.files if k.startswith("calib_")}
+    assert sorted(recorded) == sorted(mine) and all(np.array_equal(recorded[k], mine[k]) and recorded[k].dtype == mine[k].dtype for k in mine)
+    assert np.array_equal(g["velo"], scan) and g["velo"].dtype == scan.dtype
     if have_reference:
-        from oracle import ref_shim
         ref_shim.install()
         import importlib.util
         spec = importlib.util.spec_from_file_location("_ref_utils_for_test", os.path.join(REFERENCE, "reconstruct", "utils.py"))

@@ -512,6 +512,223 @@ def reconstruct_object(dec, prm, t_cam_obj, pts, rays, depth, code=None, trace=N
     return dict(t_cam_obj=_inv(t_obj_cam), code=z, is_good=True, loss=loss)
 
 
+# ----------------------------------------------------------------------------------------------
+# float64 linearisation (the yardstick of tests/gn_metric.py; not a restatement of the reference's rounding)
+# ----------------------------------------------------------------------------------------------
+F64 = np.float64
+
+
+def _mm64(a, b):
+    """(n,k) @ (k,m) float64 dgemm."""
+    a = np.ascontiguousarray(a, dtype=F64)
+    b = np.ascontiguousarray(b, dtype=F64)
+    if _torch is not None and a.shape[0] >= 64:
+        return _torch.mm(_torch.from_numpy(a), _torch.from_numpy(b)).numpy()
+    return a @ b
+
+
+# A hidden pre-activation may land on the other side of its ReLU in an fp32 implementation when it lies within that implementation's
+# round-off of zero.  Its round-off has two parts: the fp32 dot product itself (a few ulp of sum_i |w_i h_i| + |b|) and the rounding of
+# the transformed point (a few ulp of each coordinate) carried to the unit by d a / d xyz.  RELU_ULPS of both is the band.
+RELU_ULPS = 2.0
+EPS32 = 2.0 ** -24
+
+
+def _decoder_fb64(dec, x, grad=True, dp=None):
+    """decoder_forward_backward in float64 on the float32 weights (cast exactly) -> y (N,), dy/dx (N, in_dim) or None, and dy/dx with
+    the ReLU mask flipped at every hidden unit whose pre-activation lies within its fp32 round-off band of zero (the gradient on the
+    other side of the kink, which an fp32 implementation may take; equal to dy/dx in rows without such a unit) or None.
+    dp (N, 3): the rounding scale of each point coordinate (see RELU_ULPS)."""
+    x = np.ascontiguousarray(x, dtype=F64)
+    n, n_lin = x.shape[0], len(dec.layers)
+    h, pre, near = x, [], []
+    t_x = np.zeros((3, n, x.shape[1]))                      # d x / d xyz
+    for d in range(3):
+        t_x[d, :, x.shape[1] - 3 + d] = 1.0
+    t_h = t_x
+    for k, (w, b) in enumerate(dec.layers):
+        w64 = w.astype(F64)
+        if k in dec.latent_in:
+            h = np.concatenate([h, x], axis=-1)
+            t_h = np.concatenate([t_h, t_x], axis=-1)
+        a = _mm64(h, w64.T) + b.astype(F64)
+        pre.append(a)
+        if grad and k < n_lin - 1:
+            band = EPS32 * (_mm64(np.abs(h), np.abs(w64).T) + np.abs(b.astype(F64)))
+            t_a = np.stack([_mm64(t_h[d], w64.T) for d in range(3)])
+            if dp is not None:
+                band = band + sum(np.abs(t_a[d]) * dp[:, d:d + 1] for d in range(3))
+            near.append(np.abs(a) <= RELU_ULPS * band)
+            t_h = t_a * (a > 0)
+        h = np.maximum(a, 0.0) if k < n_lin - 1 else a
+    y = np.tanh(h[:, 0])
+    if not grad:
+        return y, None, None
+
+    def backward(flip):
+        g = (1.0 - y * y)[:, None] * dec.layers[-1][0].astype(F64)
+        g_skip = np.zeros_like(x)
+        for k in range(n_lin - 2, -1, -1):
+            m = pre[k] > 0
+            if flip:
+                m = m ^ near[k]
+            g = _mm64(g * m, dec.layers[k][0].astype(F64))
+            if k in dec.latent_in:
+                g_skip = g_skip + g[:, -dec.in_dim:]
+                g = g[:, :-dec.in_dim]
+        return g + g_skip
+
+    g = backward(False)
+    return y, g, (backward(True) if any(m.any() for m in near) else g)
+
+
+def _decode64(dec, code, p, grad=True, chunk=4096, dp=None):
+    """(sdf (N,), d sdf / d[code, xyz] (N, C+3) or None, the same with near-zero ReLUs flipped or None) at float64 points p (N, 3)."""
+    n = p.shape[0]
+    ys, gs, gf = [np.zeros(0, F64)], [np.zeros((0, dec.in_dim), F64)], [np.zeros((0, dec.in_dim), F64)]
+    for h in range(0, n, chunk):
+        sub = p[h:h + chunk]
+        x = np.concatenate([np.broadcast_to(np.asarray(code, F64), (sub.shape[0], dec.code_len)), sub], -1)
+        y, g, g2 = _decoder_fb64(dec, x, grad, None if dp is None else dp[h:h + chunk])
+        ys.append(y)
+        if grad:
+            gs.append(g)
+            gf.append(g2)
+    if not grad:
+        return np.concatenate(ys), None, None
+    return np.concatenate(ys), np.concatenate(gs), np.concatenate(gf)
+
+
+def _flip_allowance(j, j_alt, rr, w):
+    """Entrywise |change| of w sum_n J_n^T J_n and of w sum_n J_n r_n when the rows j take their other-side-of-the-kink values j_alt,
+    summed over the rows that differ -> (A_H, a_b, number of rows)."""
+    rows = np.where(np.any(j_alt != j, axis=1))[0]
+    n = j.shape[1]
+    a_h, a_b = np.zeros((n, n)), np.zeros(n)
+    for r in rows:
+        a_h += w * np.abs(np.outer(j_alt[r], j_alt[r]) - np.outer(j[r], j[r]))
+        a_b += w * np.abs((j_alt[r] - j[r]) * rr[r])
+    return a_h, a_b, int(rows.shape[0])
+
+
+def _robust64(res, b):
+    """get_robust_res in float64 -> (w * res, mean((w * res)^2))."""
+    x = np.abs(res)
+    rho = np.where(x <= b, x * x, 2.0 * b * x - b * b)
+    w = np.sqrt(rho) / np.where(x == 0, 1.0, x)
+    rr = w * res
+    return rr, float(np.mean(rr * rr))
+
+
+def _sim3_rows64(p):
+    """points_to_pose_jacobian_sim3 in float64: (N,3) -> (N,3,7)."""
+    n = p.shape[0]
+    j = np.zeros((n, 3, 7), F64)
+    j[:, 0, 0] = j[:, 1, 1] = j[:, 2, 2] = 1
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    j[:, 0, 4], j[:, 0, 5] = z, -y
+    j[:, 1, 3], j[:, 1, 5] = -z, x
+    j[:, 2, 3], j[:, 2, 4] = y, -x
+    j[:, :, 6] = p
+    return j
+
+
+def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
+    """One Gauss-Newton system of reconstruct_object (optimizer.py:129-186) evaluated in float64 throughout, at the state
+    (t_obj_cam, code) with the depth samples `depths`, on the sample sets the caller decided: sets = the fp32 trace's `sets`
+    (`valid` = in-sphere (ray, depth) indices, `kept` = rendered rows).  No threshold is re-applied here -- fp64 and fp32 may
+    decide a sample within round-off of a threshold differently, and the comparison is of arithmetic on one set.
+
+    Returns a dict: H, b, dx (the system and its solve), Dr / Ds (data Grams k1 J_r^T J_r / K and k2 J_s^T J_s / N, no prior, no
+    damping), gr / gs (data parts of b: -k1 J_r^T r_r / K, -k2 J_s^T r_s / N), Lr / Ls (k1 render_loss, k2 sdf_loss), the prior
+    terms H_code_prior (k3), b_code_prior (-k3 z), H_rot / b_rot (the k4 rotation prior as added to H and b), j_rot, H_damp (the
+    pose-block damping), V, K, N, loss.  H_flip / b_flip: what the surface and render rows with a hidden ReLU within round-off of its
+    kink (RELU_ULPS) would change in H and b, entry by entry, on the other side of it -- an fp32 implementation may land on either side,
+    and the gradient jumps there (n_flip = the number of such surface and render rows)."""
+    c_len = prm.code_len
+    z = np.asarray(code, F64)[:c_len]
+    t = np.asarray(t_obj_cam, F32).astype(F64)
+    r_m, t_v = t[:3, :3], t[:3, 3]
+    rays = np.asarray(rays, F32).astype(F64)
+    d = np.asarray(depths, F32).astype(F64)[:prm.num_depth_samples]
+    n_d = d.shape[0]
+    n_fg = np.asarray(depth).shape[0]
+    d_min, d_max = d[0], d[-1]
+    c11 = float(F32(1.1))                                     # the reference's constants are float32 scalars
+    depth_obs = np.concatenate([np.asarray(depth, F32).astype(F64), np.full(rays.shape[0] - n_fg, c11 * d_max)])
+    th = float(F32(prm.cut_off))
+    pd = 7
+    # surface term (loss.py:22-43)
+    p_s = np.asarray(pts, F32).astype(F64) @ r_m.T + t_v
+    p_in = np.asarray(pts, F32).astype(F64)
+    r_s, g_s, g_s2 = _decode64(dec, z, p_s, dp=EPS32 * (np.abs(p_in) @ np.abs(r_m).T + np.abs(t_v)))
+    sim_s = _sim3_rows64(p_s)
+    j_s = np.concatenate([np.einsum("ni,nij->nj", g_s[:, -3:], sim_s), g_s[:, :-3]], -1)
+    j_s2 = np.concatenate([np.einsum("ni,nij->nj", g_s2[:, -3:], sim_s), g_s2[:, :-3]], -1)
+    rr_s, sdf_loss = _robust64(r_s, float(F32(prm.b2)))
+    # render term (loss.py:46-152) on the given sets
+    vx, vy = (np.asarray(a) for a in sets["valid"])
+    gx, gy = (np.asarray(a) for a in sets["kept"])
+    p_v = (rays[vx] * d[vy, None]) @ r_m.T + t_v
+    sdf_v = _decode64(dec, z, p_v, grad=False)[0]
+    occ = np.zeros((rays.shape[0], n_d), F64)
+    occ[vx, vy] = 0.5 - np.clip(sdf_v, -th, th) / (2.0 * th)
+    occ_g = occ[gx]                                           # (K, D): the kept rows' rays
+    acc = np.cumprod(1.0 - occ_g, axis=-1)
+    acc_aug = np.concatenate([np.ones((gx.shape[0], 1)), acc], -1)
+    o = np.concatenate([occ_g, np.ones((gx.shape[0], 1))], -1)
+    dd = np.concatenate([d, [c11 * d_max]])
+    d_u = np.sum(dd * o * acc_aug, axis=-1)
+    o_k = occ[gx, gy]
+    acc_z = np.where(np.arange(n_d)[None, :] < gy[:, None], 0.0, acc)
+    de_do = np.sum(acc_z, axis=-1) / (1.0 - o_k)
+    de_ds = de_do * ((d_max - d_min) / (n_d - 1)) * (-1.0 / (2.0 * th))
+    r_r = np.clip(depth_obs[gx] - d_u, -float(F32(0.30)), float(F32(0.30)))
+    p_k = (rays[gx] * d[gy, None]) @ r_m.T + t_v
+    p_cam = rays[gx] * d[gy, None]
+    _, ds_di, ds_di2 = _decode64(dec, z, p_k, dp=EPS32 * (2 * np.abs(p_cam) @ np.abs(r_m).T + np.abs(t_v)))
+    sim_k = _sim3_rows64(p_k)
+    de_di, de_di2 = de_ds[:, None] * ds_di, de_ds[:, None] * ds_di2
+    j_r = np.concatenate([np.einsum("ni,nij->nj", de_di[:, -3:], sim_k), de_di[:, :-3]], -1)
+    j_r2 = np.concatenate([np.einsum("ni,nij->nj", de_di2[:, -3:], sim_k), de_di2[:, :-3]], -1)
+    rr_r, render_loss = _robust64(r_r, float(F32(prm.b1)))
+    # rotation prior (loss.py:155-178)
+    t_co = np.linalg.inv(t)
+    r_co = t_co[:3, :3] / np.cbrt(np.linalg.det(t_co[:3, :3]))
+    res_rot = 1.0 + r_co[1, 1]
+    j_rot = np.zeros(pd)
+    if res_rot >= 1e-7:
+        j_rot[3:6] = np.cross(np.linalg.inv(r_co) @ np.array([0., -1., 0.]), np.array([0., 1., 0.]))
+    else:
+        res_rot = 0.0
+    k1, k2, k3, k4 = (float(F32(v)) for v in (prm.k1, prm.k2, prm.k3, prm.k4))
+    n_s, n_k = j_s.shape[0], j_r.shape[0]
+    ds_ = k2 * _mm64(j_s.T, j_s) / n_s
+    dr_ = k1 * _mm64(j_r.T, j_r) / n_k
+    gs_ = -k2 * (j_s.T @ rr_s) / n_s
+    gr_ = -k1 * (j_r.T @ rr_r) / n_k
+    fh_s, fb_s, nf_s = _flip_allowance(j_s, j_s2, rr_s, k2 / n_s)
+    fh_r, fb_r, nf_r = _flip_allowance(j_r, j_r2, rr_r, k1 / n_k)
+    n_unk = pd + c_len
+    h_code = np.zeros((n_unk, n_unk))
+    h_code[pd:, pd:] = k3 * np.eye(c_len)
+    b_code = np.zeros(n_unk)
+    b_code[pd:] = -k3 * z
+    h_rot = np.zeros((n_unk, n_unk))
+    h_rot[:pd, :pd] = k4 * np.outer(j_rot, j_rot)
+    b_rot = np.zeros(n_unk)
+    b_rot[:pd] = k4 * j_rot * res_rot
+    h_damp = np.zeros((n_unk, n_unk))
+    h_damp[:pd, :pd] = np.eye(pd)
+    h_damp[pd - 1, pd - 1] += float(F32(prm.s_damp))
+    h = dr_ + ds_ + h_code + h_rot + h_damp
+    b = gr_ + gs_ + b_code + b_rot
+    return dict(H=h, b=b, dx=np.linalg.solve(h, b), Dr=dr_, Ds=ds_, gr=gr_, gs=gs_, Lr=k1 * render_loss, Ls=k2 * sdf_loss,
+                H_code_prior=h_code, b_code_prior=b_code, H_rot=h_rot, b_rot=b_rot, j_rot=j_rot, res_rot=res_rot, H_damp=h_damp,
+                H_flip=fh_s + fh_r, b_flip=fb_s + fb_r, n_flip=(nf_s, nf_r),
+                V=int(vx.shape[0]), K=int(n_k), N=int(n_s), loss=k1 * render_loss + k2 * sdf_loss)
+
+
 def estimate_pose_cam_obj(dec, prm, t_co_se3, scale, pts, code, trace=None):
     """Optimizer.estimate_pose_cam_obj (optimizer.py:45-86) -> (4,4) f32 SE(3) object->camera.
 

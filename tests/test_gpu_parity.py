@@ -13,6 +13,7 @@ import json
 import numpy as np
 import pytest
 
+import gn_metric as M
 from conftest import golden, parity_log
 from oracle import dsp_oracle as O
 from dsp_slam_amd import fixtures, synth, engine as E
@@ -163,8 +164,12 @@ def compare_linearisation(tr, i, its, k4, tol_b=1e-4):
     that dominate H.  So the bound is 1e-4 relative PLUS what the oracle itself moves under that round-off -- when both
     implementations selected exactly the same sample SETS (membership checksums, not just counts).  A sample within
     round-off of a threshold may legitimately switch sets; then the comparison is O(flips / K) and says so.
+    its may carry a fourth element, the fp64 linearisation on the oracle's sets (one_iteration_oracle): where the sets are identical the
+    device's system is then also checked entry by entry against it (tests/gn_metric.py: every block within TAU of fp64, with the jitter
+    twin's allowance), in addition to the max-norm bounds above it.
     Returns True when the strict comparison was made."""
-    it, itj, own_depths = its
+    it, itj, own_depths = its[:3]
+    lin = its[3] if len(its) > 3 else None
     nd = own_depths.shape[0]
     assert np.abs(tr["depths"][i][:nd] - own_depths).max() <= 2.5 * np.spacing(np.abs(own_depths).max())
     same_sets = int(tr["set_sums"][i][0]) == it["vsum"] and int(tr["set_sums"][i][1]) == it["ksum"]
@@ -190,13 +195,19 @@ def compare_linearisation(tr, i, its, k4, tol_b=1e-4):
         tol_bv[3:6] = np.maximum(tol_bv[3:6], tol_rot)
         tol_dx = np.abs(np.linalg.inv(it["H"].astype(np.float64))) @ tol_bv
         assert np.all(np.abs(tr["dx"][i] - it["dx"]) <= 2e-4 * np.abs(it["dx"]).max() + 2 * np.abs(itj["dx"] - it["dx"]).max() + tol_dx)
+        LAST_LINEARISATION.clear()
         LAST_LINEARISATION.update(same_sets=True, flips=0, rel_H=float(np.abs(tr["H"][i] - it["H"]).max() / hs),
                                   rel_b=float(np.abs(tr["b"][i][mask] - it["b"][mask]).max() / bs), oracle_jitter_rel_H=float(amp_h / hs),
                                   V=int(it["V"]), K=int(it["K"]))
+        if lin is not None:
+            assert (lin["V"], lin["K"]) == (it["V"], it["K"])
+            LAST_LINEARISATION["fp64"] = M.check_against_fp64(dict(H=tr["H"][i], b=tr["b"][i], dx=tr["dx"][i]), lin, lin["k4"], pair=(it, itj),
+                                                              what="object %d, V %d K %d" % (i, it["V"], it["K"]))
         return amp_h < 1e-3 * hs
     assert flips <= max(4, it["K"] // 250), "too many threshold flips: V %d/%d m %d/%d K %d/%d" % (
         tr["V"][i], it["V"], tr["m"][i], it["m"], tr["K"][i], it["K"])   # m informational
     loose = 8.0 * max(flips, 2) / max(it["K"], 1)
+    LAST_LINEARISATION.clear()
     LAST_LINEARISATION.update(same_sets=False, flips=int(flips), rel_H=float(np.abs(tr["H"][i] - it["H"]).max() / hs),
                               rel_b=float(np.abs(tr["b"][i][mask] - it["b"][mask]).max() / bs),
                               oracle_jitter_rel_H=float(np.abs(itj["H"] - it["H"]).max() / hs), V=int(it["V"]), K=int(it["K"]))
@@ -205,7 +216,9 @@ def compare_linearisation(tr, i, its, k4, tol_b=1e-4):
     return False
 
 
-def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0):
+def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0, fp64=True):
+    """(oracle trace on the device's depth samples, the same with the sdf jittered, the oracle's own depth samples[, the fp64
+    linearisation on the first one's sets, its `k4` added]) at object i's state of the device trace tr."""
     o1 = O.GNParams(oprm.k1, oprm.k2, oprm.k3, oprm.k4, oprm.b1, oprm.b2, oprm.lr, oprm.s_damp, 1, oprm.code_len,
                     oprm.num_depth_samples, oprm.cut_off)
     out = []
@@ -218,6 +231,11 @@ def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0):
     O.reconstruct_object(oracle_decoder, o1, None, obj["pts"], obj["rays"], obj["depth"], tr["code"][i], trace=otr,
                          t_obj_cam0=tr["t_obj_cam"][i])
     out.append(otr[0]["depths"])
+    if fp64:
+        lin = O.linearise_fp64(oracle_decoder, oprm, obj["pts"], obj["rays"], obj["depth"], tr["t_obj_cam"][i], tr["code"][i], tr["depths"][i],
+                               out[0]["sets"])
+        lin["k4"] = oprm.k4
+        out.append(lin)
     return tuple(out)
 
 
@@ -253,7 +271,8 @@ def _check_iterations(oracle_decoder, obj, traces, oprm, k4, name="", explain=No
             named.append(dict(iteration=e, flips=[(f["ray"], f["depth_index"], f["threshold"], f["margin"]) for f in fl]))
     parity_log(kind="iterations", case=name, n=len(traces), strict=strict, same_sets=sum(1 for p in per_iter if p["same_sets"]),
                flips=[p["flips"] for p in per_iter], rel_H=[p["rel_H"] for p in per_iter], rel_b=[p["rel_b"] for p in per_iter],
-               oracle_jitter_rel_H=[p["oracle_jitter_rel_H"] for p in per_iter], K=[p["K"] for p in per_iter], named_flips=named)
+               oracle_jitter_rel_H=[p["oracle_jitter_rel_H"] for p in per_iter], K=[p["K"] for p in per_iter], named_flips=named,
+               fp64=[p.get("fp64") for p in per_iter])
     n_same = sum(1 for p in per_iter if p["same_sets"])
     assert n_same + len(named) == len(traces) and len(named) <= 1, "iterations whose sets differ from the oracle's: %s" % named      # measured on MI355X: 0
 

@@ -20,6 +20,7 @@ GRAD_DIM = 67
 
 OBJ_GOOD, OBJ_FEW_SAMPLES, OBJ_NAN = 0, 1, 2
 PREPASS_OFF, PREPASS_F16, PREPASS_BF16 = 0, 1, 2
+MESH_REGULAR_GRID, MESH_PREPASS_F16, MESH_PREPASS_BF16 = 1, 2, 4     # dsp_extract_mesh(es) flags
 PREPASS_SMALL_TILES = 0x100
 COMPUTE_F32, COMPUTE_F16, COMPUTE_BF16 = 0, 1, 2
 # keys of dsp_batch_set_debug (include/dsp_gn.h: DSP_DBG_*)
@@ -114,6 +115,9 @@ SYMBOLS = [
     ("dsp_extract_mesh", C.c_int, [_VP, c_f32p, C.c_int32, C.c_int32, c_i64p, c_i64p]),
     ("dsp_marching_cubes", C.c_int, [_VP, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, c_i64p, c_i64p]),
     ("dsp_mesh_fetch", C.c_int, [_VP, c_f32p, C.c_int64, c_i32p, C.c_int64]),
+    ("dsp_extract_meshes", C.c_int, [_VP, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, c_i64p, c_i64p]),
+    ("dsp_meshes_fetch", C.c_int, [_VP, C.c_int64, c_i64p, c_i64p, c_f32p, c_i32p]),
+    ("dsp_mesh_last_stats", C.c_int, [_VP, c_i64p, c_f32p]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

@@ -347,5 +347,18 @@ hipError_t launch_mc_count(const float* vol, int n0, int n1, int n2, float level
                            hipStream_t s);
 hipError_t launch_mc_emit(const float* vol, int n0, int n1, int n2, float level, const McTables* tab, const int2* block_off, float spacing,
                           float origin, float* verts, int* vidmap, int* faces, hipStream_t s);
+// batched extraction: n_obj volumes of n^3 back to back (object-major); block sums [n_obj][mc_num_blocks(n^3)] scanned as one list,
+// obj_base[o] = first (vertex, face) of object o inside the chunk's output
+hipError_t launch_mc_count_batched(const float* vol, int n, int n_obj, float level, const McTables* tab, int2* block_sums, long long* totals,
+                                   int2* obj_base, hipStream_t s);
+hipError_t launch_mc_emit_batched(const float* vol, int n, int n_obj, float level, const McTables* tab, const int2* block_off, float spacing,
+                                  float origin, float* verts, int* vidmap, int* faces, hipStream_t s);
+// surface band of n_obj prepass volumes (k_mesh_band): selected points compacted per object into the band lists (capacity n^3 each),
+// cnt = [n_obj] selected + [n_obj] of them audited (zeroed by the caller), and the fp32 kernel's tile list over them (tiles: capacity
+// n_obj x ceil(n^3 / MESH_TILE_PTS); *n_tiles on the device).  guard: per object {delta, trips, max err}, delta read here
+constexpr int MESH_TILE_PTS = TILE_PTS;
+hipError_t launch_mesh_band(const float* lp, const float4* grid, int n, int n_obj, const unsigned* guard, float4* band_pts, float* band_val,
+                            long long* band_idx, int* cnt, int* tile0, int* n_tiles, int4* tiles, hipStream_t s);
+hipError_t launch_mesh_scatter(const float* band_val, const long long* band_idx, const int* cnt, int n, int n_obj, float* vol, hipStream_t s);
 
 }  // namespace dsp

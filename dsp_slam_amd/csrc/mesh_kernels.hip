@@ -344,6 +344,182 @@ __global__ void k_grid_points(float4* pts, int n, float voxel_size, int regular)
                          __fadd_rn(__fmul_rn(fk, voxel_size), -1.f), 0.f);
 }
 
+// ---- batched extraction (extract_meshes_impl, dsp_gn.hip) -------------------------------------------------------------------
+// n_obj volumes of the same grid, back to back.  The marching-cubes kernels below are the ones above with the object taken from
+// blockIdx.y; their block sums form ONE list (object-major) that k_mc_scan scans across the whole chunk, so every object's vertices
+// and faces land in their own contiguous range in the order dsp_extract_mesh produces.  Vertex ids in vidmap are chunk-global; faces
+// subtract the object's first vertex id, so face indices stay local to their mesh.
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_count_b(const float* vol, Dims d, float level, int n_pts, const McTables* tab, int2* block_sums) {
+    __shared__ int2 sh[MC_BLOCK];
+    const int g = blockIdx.x * MC_BLOCK + threadIdx.x, obj = blockIdx.y;
+    int nv, cfg, nt;
+    bool cross[3];
+    mc_classify(vol + (size_t)obj * n_pts, d, level, g, n_pts, tab, nv, cfg, nt, cross);
+    int2 total;
+    block_scan(make_int2(nv, nt), sh, total);
+    if (threadIdx.x == 0) block_sums[(size_t)obj * gridDim.x + blockIdx.x] = total;
+}
+
+// first (vertex, face) of every object: the scanned sum of its first block
+__global__ void k_mc_obj_base(const int2* block_off, int nb, int n_obj, int2* base) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o < n_obj) base[o] = block_off[(size_t)o * nb];
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_verts_b(const float* vol, Dims d, float level, int n_pts, const McTables* tab,
+                                                         const int2* block_off, float spacing, float origin, float* verts, int* vidmap) {
+    __shared__ int2 sh[MC_BLOCK];
+    const int g = blockIdx.x * MC_BLOCK + threadIdx.x, obj = blockIdx.y;
+    const float* v = vol + (size_t)obj * n_pts;
+    int nv, cfg, nt;
+    bool cross[3];
+    mc_classify(v, d, level, g, n_pts, tab, nv, cfg, nt, cross);
+    int2 total;
+    const int2 off = block_scan(make_int2(nv, nt), sh, total);
+    if (nv == 0) return;
+    int i, j, k;
+    unravel(g, d, i, j, k);
+    const int stride[3] = {d.n1 * d.n2, d.n2, 1};
+    const float s0 = v[g];
+    int vid = block_off[(size_t)obj * gridDim.x + blockIdx.x].x + off.x;
+    int* vm = vidmap + (size_t)obj * 3 * n_pts;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!cross[a]) continue;
+        const float s1 = v[g + stride[a]];
+        const float t = __fdiv_rn(__fsub_rn(level, s0), __fsub_rn(s1, s0));
+        float p[3] = {(float)i, (float)j, (float)k};
+        p[a] = __fadd_rn(p[a], t);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) verts[3 * (size_t)vid + c] = __fadd_rn(__fmul_rn(p[c], spacing), origin);
+        vm[3 * (size_t)g + a] = vid;
+        ++vid;
+    }
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void k_mc_faces_b(const float* vol, Dims d, float level, int n_pts, const McTables* tab,
+                                                         const int2* block_off, const int* vidmap, int* faces) {
+    __shared__ int2 sh[MC_BLOCK];
+    const int g = blockIdx.x * MC_BLOCK + threadIdx.x, obj = blockIdx.y;
+    int nv, cfg, nt;
+    bool cross[3];
+    mc_classify(vol + (size_t)obj * n_pts, d, level, g, n_pts, tab, nv, cfg, nt, cross);
+    int2 total;
+    const int2 off = block_scan(make_int2(nv, nt), sh, total);
+    if (nt == 0) return;
+    const int s1 = d.n2, s0 = d.n1 * d.n2;
+    const int v0 = block_off[(size_t)obj * gridDim.x].x;          // the object's first vertex
+    const int* vm = vidmap + (size_t)obj * 3 * n_pts;
+    const size_t f0 = (size_t)block_off[(size_t)obj * gridDim.x + blockIdx.x].y + off.y;
+    for (int t = 0; t < nt; ++t)
+        for (int c = 0; c < 3; ++c) {
+            const int e = tab->tri[cfg][3 * t + c];
+            const int go = g + tab->edge_off[e][0] * s0 + tab->edge_off[e][1] * s1 + tab->edge_off[e][2];
+            faces[3 * (f0 + t) + c] = vm[3 * (size_t)go + tab->edge_off[e][3]] - v0;
+        }
+}
+
+// ---- surface band of a prepass volume (DESIGN.md "Mesh extraction") ---------------------------------------------------------
+// Class of a prepass value against the object's margin: +1 (lp >= delta), -1 (lp <= -delta), 0 = uncertain (|lp| < delta, NaN, inf).
+__device__ __forceinline__ int band_class(float x, float delta) {
+    if (!isfinite(x)) return 0;
+    return x >= delta ? 1 : (x <= -delta ? -1 : 0);
+}
+
+// fixed hash of (object, grid point): the stratified audit's choice (the same points every call)
+__device__ __forceinline__ unsigned band_hash(unsigned c, unsigned g) {
+    unsigned x = g * 0x9E3779B1u ^ (c + 0x7F4A7C15u) * 0x85EBCA77u;
+    x ^= x >> 15; x *= 0x2C1B3C6Du;
+    x ^= x >> 12; x *= 0x297A2D39u;
+    return x ^ (x >> 15);
+}
+
+// One thread per grid point g of volume c (blockIdx.y).  A point needs its fp32 value when it is uncertain, or when one of its <= 6
+// axis neighbours inside the grid is uncertain or certain of the opposite sign: then every sign marching cubes reads is certified
+// and every value it interpolates is fp32.  Audit: 1/8 of the certain points with |lp| < 2 delta and 1/512 of the rest go to the fp32
+// kernel too, so that its guard also looks at classified points.  Selected points are compacted per object (one atomic per wave,
+// ballot order inside it) into [c * n, c * n + cnt[c]) of the point / value / index lists; the value list holds lp, which the fp32
+// kernel's guard compares with what it stores there.  cnt = [n_obj] selected, [n_obj] audited; guard = per object {delta, trips, max err}.
+__global__ __launch_bounds__(256) void k_mesh_band(const float* __restrict__ lp, const float4* __restrict__ grid, int n, int n_pts,
+                                                   const unsigned* __restrict__ guard, float4* band_pts, float* band_val,
+                                                   long long* band_idx, int* cnt, int n_obj) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const float delta = __uint_as_float(guard[3 * c]);
+    const float* v = lp + (size_t)c * n_pts;
+    bool need = false, audit = false;
+    float x = 0.f;
+    if (g < n_pts) {
+        x = v[g];
+        const int own = band_class(x, delta);
+        need = own == 0;
+        if (!need) {
+            const int k = g % n, j = (g / n) % n, i = g / (n * n);
+            const int s1 = n, s0 = n * n;
+            int nb[6], m = 0;
+            if (i > 0) nb[m++] = g - s0;
+            if (i + 1 < n) nb[m++] = g + s0;
+            if (j > 0) nb[m++] = g - s1;
+            if (j + 1 < n) nb[m++] = g + s1;
+            if (k > 0) nb[m++] = g - 1;
+            if (k + 1 < n) nb[m++] = g + 1;
+            for (int q = 0; q < m; ++q) {
+                const int o = band_class(v[nb[q]], delta);
+                if (o != own) { need = true; break; }       // uncertain (0) or the opposite sign
+            }
+        }
+        if (!need) audit = (band_hash((unsigned)c, (unsigned)g) & (fabsf(x) < 2.f * delta ? 7u : 511u)) == 0u;
+    }
+    const bool sel = need || audit;
+    const unsigned long long m = __ballot(sel), ma = __ballot(audit);
+    if (m == 0ull) return;
+    int base = 0;
+    if (lane == 0) {
+        base = atomicAdd(cnt + c, __popcll(m));
+        if (ma) atomicAdd(cnt + n_obj + c, __popcll(ma));
+    }
+    base = __shfl(base, 0);
+    if (!sel) return;
+    const size_t o = (size_t)c * n_pts + base + __popcll(m & ((1ull << lane) - 1ull));
+    band_pts[o] = grid[g];
+    band_val[o] = x;
+    band_idx[o] = (long long)c * n_pts + g;
+}
+
+// tile list of the fp32 kernel over the band lists: object c's tiles {c * n + 64 i, points, c, 0} follow those of objects < c.
+// One block: per-object tile counts scanned (n_obj <= 1024), first tile of every object into tile0[c], the total into *n_tiles.
+__global__ __launch_bounds__(1024) void k_mesh_tile_scan(const int* cnt, int n_obj, int* tile0, int* n_tiles) {
+    __shared__ int sh[1024];
+    const int t = threadIdx.x;
+    const int nt = t < n_obj ? (cnt[t] + MESH_TILE_PTS - 1) / MESH_TILE_PTS : 0;
+    sh[t] = nt;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int add = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    if (t < n_obj) tile0[t] = sh[t] - nt;
+    if (t == 1023) *n_tiles = sh[t];
+}
+
+__global__ void k_mesh_tiles(const int* cnt, const int* tile0, int n_pts, int4* tiles) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+    const int first = i * MESH_TILE_PTS;
+    if (first >= cnt[c]) return;
+    tiles[tile0[c] + i] = make_int4(c * n_pts + first, min(MESH_TILE_PTS, cnt[c] - first), c, 0);
+}
+
+// the band's fp32 values into the volumes at their flat index (every other entry keeps its prepass value of certified sign)
+__global__ void k_mesh_scatter(const float* band_val, const long long* band_idx, const int* cnt, int n_pts, float* vol) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+    if (i >= cnt[c]) return;
+    const size_t o = (size_t)c * n_pts + i;
+    vol[band_idx[o]] = band_val[o];
+}
+
 }  // namespace
 
 int mc_num_blocks(int n_pts) { return (n_pts + MC_BLOCK - 1) / MC_BLOCK; }
@@ -369,6 +545,42 @@ hipError_t launch_mc_emit(const float* vol, int n0, int n1, int n2, float level,
     const Dims d{n0, n1, n2};
     hipLaunchKernelGGL(k_mc_verts, dim3(nb), dim3(MC_BLOCK), 0, s, vol, d, level, n_pts, tab, block_off, spacing, origin, verts, vidmap);
     hipLaunchKernelGGL(k_mc_faces, dim3(nb), dim3(MC_BLOCK), 0, s, vol, d, level, n_pts, tab, block_off, vidmap, faces);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_count_batched(const float* vol, int n, int n_obj, float level, const McTables* tab, int2* block_sums, long long* totals,
+                                   int2* obj_base, hipStream_t s) {
+    const int n_pts = n * n * n, nb = mc_num_blocks(n_pts);
+    const Dims d{n, n, n};
+    hipLaunchKernelGGL(k_mc_count_b, dim3(nb, n_obj), dim3(MC_BLOCK), 0, s, vol, d, level, n_pts, tab, block_sums);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, block_sums, nb * n_obj, totals);
+    hipLaunchKernelGGL(k_mc_obj_base, dim3((n_obj + 255) / 256), dim3(256), 0, s, block_sums, nb, n_obj, obj_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_emit_batched(const float* vol, int n, int n_obj, float level, const McTables* tab, const int2* block_off, float spacing,
+                                  float origin, float* verts, int* vidmap, int* faces, hipStream_t s) {
+    const int n_pts = n * n * n, nb = mc_num_blocks(n_pts);
+    const Dims d{n, n, n};
+    hipLaunchKernelGGL(k_mc_verts_b, dim3(nb, n_obj), dim3(MC_BLOCK), 0, s, vol, d, level, n_pts, tab, block_off, spacing, origin, verts, vidmap);
+    hipLaunchKernelGGL(k_mc_faces_b, dim3(nb, n_obj), dim3(MC_BLOCK), 0, s, vol, d, level, n_pts, tab, block_off, vidmap, faces);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_band(const float* lp, const float4* grid, int n, int n_obj, const unsigned* guard, float4* band_pts, float* band_val,
+                            long long* band_idx, int* cnt, int* tile0, int* n_tiles, int4* tiles, hipStream_t s) {
+    const int n_pts = n * n * n;
+    hipLaunchKernelGGL(k_mesh_band, dim3((n_pts + 255) / 256, n_obj), dim3(256), 0, s, lp, grid, n, n_pts, guard, band_pts, band_val, band_idx,
+                       cnt, n_obj);
+    hipLaunchKernelGGL(k_mesh_tile_scan, dim3(1), dim3(1024), 0, s, cnt, n_obj, tile0, n_tiles);
+    const int max_tiles = (n_pts + MESH_TILE_PTS - 1) / MESH_TILE_PTS;
+    hipLaunchKernelGGL(k_mesh_tiles, dim3((max_tiles + 255) / 256, n_obj), dim3(256), 0, s, cnt, tile0, n_pts, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_scatter(const float* band_val, const long long* band_idx, const int* cnt, int n, int n_obj, float* vol, hipStream_t s) {
+    const int n_pts = n * n * n;
+    hipLaunchKernelGGL(k_mesh_scatter, dim3((n_pts + 255) / 256, n_obj), dim3(256), 0, s, band_val, band_idx, cnt, n_pts, vol);
     return hipGetLastError();
 }
 

@@ -361,14 +361,53 @@ class Engine(object):
         L.check(L.load().dsp_mesh_fetch(self._h, L.ptr(verts), nv.value, L.ptr(faces, L.c_i32p), nf.value), self._h, "dsp_mesh_fetch")
         return verts, faces
 
-    def extract_mesh(self, code, vol_dim, regular_grid=False):
+    @staticmethod
+    def _mesh_flags(regular_grid, prepass):
+        """flags word of dsp_extract_mesh(es): prepass None / "off" / PREPASS_OFF, "f16" / PREPASS_F16 or "bf16" / PREPASS_BF16."""
+        lp = {None: 0, "off": 0, L.PREPASS_OFF: 0, "f16": L.MESH_PREPASS_F16, L.PREPASS_F16: L.MESH_PREPASS_F16,
+              "bf16": L.MESH_PREPASS_BF16, L.PREPASS_BF16: L.MESH_PREPASS_BF16}.get(prepass)
+        if lp is None:
+            raise ValueError("prepass must be None, 'off', 'f16' or 'bf16', not %r" % (prepass,))
+        return (L.MESH_REGULAR_GRID if regular_grid else 0) | lp
+
+    def extract_mesh(self, code, vol_dim, regular_grid=False, prepass=None):
         """Grid decode + marching cubes on the device (the SDF volume never leaves HBM): vertices (V,3) float32 in the
         decoder's [-1,1]^3 frame, faces (F,3) int32.  Empty when the surface does not cross the grid.  regular_grid=False
-        samples the reference's (sheared) grid, see reconstruct.utils.create_voxel_grid."""
+        samples the reference's (sheared) grid, see reconstruct.utils.create_voxel_grid.  prepass="f16" / "bf16": the grid goes
+        through the low-precision prepass and only its surface band through the fp32 kernel -- the same mesh, bit for bit
+        (dsp_extract_meshes)."""
         code = L.code64(code)
         nv, nf = C.c_int64(0), C.c_int64(0)
-        L.check(L.load().dsp_extract_mesh(self._h, L.ptr(code), int(vol_dim), 1 if regular_grid else 0, C.byref(nv), C.byref(nf)), self._h, "dsp_extract_mesh")
+        L.check(L.load().dsp_extract_mesh(self._h, L.ptr(code), int(vol_dim), self._mesh_flags(regular_grid, prepass), C.byref(nv), C.byref(nf)),
+                self._h, "dsp_extract_mesh")
         return self._fetch_mesh(nv, nf)
+
+    def extract_meshes(self, codes, vol_dim, regular_grid=False, prepass=None, delta=0.0):
+        """The meshes of n objects on one grid in a few launches (dsp_extract_meshes): a list of (vertices, faces), each equal to
+        extract_mesh of that code; an object whose surface misses the grid gets empty arrays.  delta > 0 forces the prepass margin
+        of every object (tests)."""
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        n = codes.shape[0]
+        if n == 0:
+            return []
+        nv, nf = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        lib = L.load()
+        L.check(lib.dsp_extract_meshes(self._h, L.ptr(codes), n, int(vol_dim), self._mesh_flags(regular_grid, prepass), float(delta),
+                                       L.ptr(nv, L.c_i64p), L.ptr(nf, L.c_i64p)), self._h, "dsp_extract_meshes")
+        verts = np.zeros((int(nv.sum()), 3), np.float32)
+        faces = np.zeros((int(nf.sum()), 3), np.int32)
+        L.check(lib.dsp_meshes_fetch(self._h, n, L.ptr(nv, L.c_i64p), L.ptr(nf, L.c_i64p), L.ptr(verts), L.ptr(faces, L.c_i32p)), self._h,
+                "dsp_meshes_fetch")
+        ov, of = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(nf)])
+        return [(verts[ov[i]:ov[i + 1]], faces[of[i]:of[i + 1]]) for i in range(n)]
+
+    def mesh_stats(self):
+        """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
+        c = np.zeros(5, np.int64)
+        e = C.c_float(0.0)
+        L.check(L.load().dsp_mesh_last_stats(self._h, L.ptr(c, L.c_i64p), C.byref(e)), self._h, "dsp_mesh_last_stats")
+        return {"prepass_points": int(c[0]), "band_points": int(c[1]), "audit_points": int(c[2]), "dense_points": int(c[3]),
+                "reruns": int(c[4]), "max_guard_err": float(e.value)}
 
     def marching_cubes(self, volume, level=0.0, spacing=1.0, origin=0.0):
         """Marching cubes of a host volume on the device: vertices = index * spacing + origin."""

@@ -107,13 +107,17 @@ class Optimizer(object):
 
 
 class MeshExtractor(object):
-    def __init__(self, decoder, code_len=64, voxels_dim=64, regular_grid=False):
+    def __init__(self, decoder, code_len=64, voxels_dim=64, regular_grid=False, prepass=None):
         """regular_grid=False samples the SDF exactly where the reference does (its grid is sheared by a true-division quirk,
-        see reconstruct.utils.create_voxel_grid); True samples the regular lattice.  (Addition; the reference has no such switch.)"""
+        see reconstruct.utils.create_voxel_grid); True samples the regular lattice.  prepass=None (default) decodes every grid point
+        in fp32; "f16" / "bf16" decodes the grid with the low-precision prepass and only the surface band in fp32 -- the same meshes,
+        bit for bit (include/dsp_gn.h dsp_extract_meshes); it does not pay at 32^3 (profiles/mesh_band.md).  (Additions; the
+        reference has no such switches.)"""
         self.decoder = decoder
         self.code_len = code_len
         self.voxels_dim = voxels_dim
         self.regular_grid = bool(regular_grid)
+        self.prepass = prepass
         self.voxel_points = create_voxel_grid(vol_dim=self.voxels_dim, regular=self.regular_grid)
 
     def decode_grid(self, code):
@@ -133,8 +137,16 @@ class MeshExtractor(object):
         """Grid decode + marching cubes, both on the GPU without the volume leaving HBM (reference optimizer.py:214-223;
         there: GPU decode, then scikit-image marching cubes on the CPU)."""
         start = get_time()
-        vertices, faces = self.decoder.engine.extract_mesh(_f32(code)[:self.code_len], self.voxels_dim, regular_grid=self.regular_grid)
+        vertices, faces = self.decoder.engine.extract_mesh(_f32(code)[:self.code_len], self.voxels_dim, regular_grid=self.regular_grid,
+                                                           prepass=self.prepass)
         if vertices.shape[0] == 0:
             raise ValueError("Surface level must be within volume data range.")   # what scikit-image raises in the reference
         print("Extract mesh takes %f seconds" % (get_time() - start))
         return ForceKeyErrorDict(vertices=vertices, faces=faces)
+
+    def extract_meshes_from_codes(self, codes):
+        """extract_mesh_from_code for many objects in one batched call (dsp_extract_meshes): a list of the same dicts, in the order
+        of `codes`.  An object whose surface does not cross the grid gets empty (0, 3) arrays instead of raising.  (Addition.)"""
+        codes = [_f32(c)[:self.code_len] for c in codes]
+        meshes = self.decoder.engine.extract_meshes(codes, self.voxels_dim, regular_grid=self.regular_grid, prepass=self.prepass)
+        return [ForceKeyErrorDict(vertices=v, faces=f) for v, f in meshes]

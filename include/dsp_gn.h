@@ -205,7 +205,29 @@ int dsp_estimate_pose_batch(dsp_handle* h, const dsp_gn_params* prm, int32_t n_o
  * An empty mesh (no sign change) is n_vertices = n_faces = 0 and not an error here (the Python mirror raises scikit-image's
  * ValueError for it).  The case table is a generated classic table, not Lewiner's: see oracle/mc_oracle.py. */
 #define DSP_MESH_REGULAR_GRID 1   /* flags: sample the regular lattice instead of the reference's sheared grid (see below) */
+#define DSP_MESH_PREPASS_F16 2    /* flags: decode the grid with the f16 prepass kernel and only the surface band in fp32 (see dsp_extract_meshes) */
+#define DSP_MESH_PREPASS_BF16 4   /* flags: the same with the bf16 prepass kernel (at most one of the two) */
 int dsp_extract_mesh(dsp_handle* h, const float* code, int32_t vol_dim, int32_t flags, int64_t* n_vertices, int64_t* n_faces);
+/* Batched extraction: the meshes of n_codes objects (codes: n_codes x 64) on one vol_dim^3 grid, in chunks that fit a fixed device
+ * budget.  n_vertices[i] / n_faces[i] receive object i's mesh size (0 / 0 when its surface does not cross the grid: not an error);
+ * dsp_meshes_fetch copies them.  Each object's mesh is, bit for bit and in the same order, what dsp_extract_mesh returns for it.
+ * Without a DSP_MESH_PREPASS_* flag every grid point is decoded in fp32.  With one, the low-precision prepass decodes every grid
+ * point; a point gets its fp32 value when its prepass value lies within the object's margin delta of 0 (or is not finite), or when one
+ * of its axis neighbours does or is certain of the other sign -- so every sign marching cubes reads is certified and every value it
+ * interpolates is fp32 -- plus a fixed stratified audit sample of the rest.  The fp32 kernel's guard compares both values; an object
+ * with a difference of delta / 2 or more is decoded densely in fp32 again.  delta <= 0: the margin calibrated at dsp_create for the
+ * object's code magnitude (the table is read, never changed by a mesh call); delta > 0: that margin for every object.  A decoder
+ * without a prepass kernel refuses the flags (DSP_E_ARG). */
+int dsp_extract_meshes(dsp_handle* h, const float* codes, int64_t n_codes, int32_t vol_dim, int32_t flags, float delta, int64_t* n_vertices,
+                       int64_t* n_faces);
+/* Copies the meshes of the last dsp_extract_meshes on this handle, concatenated in object order: vertices (sum n_vertices) x 3 float32,
+ * faces (sum n_faces) x 3 int32, face indices local to their own mesh.  n_codes / n_vertices / n_faces must be what that call returned,
+ * else nothing is copied and DSP_E_STATE is returned. */
+int dsp_meshes_fetch(dsp_handle* h, int64_t n_codes, const int64_t* n_vertices, const int64_t* n_faces, float* vertices, int32_t* faces);
+/* Counts of the last mesh extraction on this handle (dsp_extract_mesh or dsp_extract_meshes): counts5 = {grid points decoded by the
+ * prepass, fp32 points of the surface band, fp32 points of the audit, grid points decoded densely in fp32 (no prepass, or objects
+ * re-run), objects re-run densely after a guard trip}; max_guard_err (optional) = largest |prepass - fp32| the guard saw. */
+int dsp_mesh_last_stats(dsp_handle* h, int64_t* counts5, float* max_guard_err);
 /* The marching-cubes step alone on a host volume (n0 x n1 x n2, axis 0 slowest): vertices = index * spacing + origin
  * (replaces convert_sdf_voxels_to_mesh, utils.py:119-140, with spacing = 2 / (n - 1), origin = -1, level = 0). */
 int dsp_marching_cubes(dsp_handle* h, const float* volume, int32_t n0, int32_t n1, int32_t n2, float level, float spacing, float origin,

@@ -3,7 +3,11 @@
 D^3 SDF grid of ALL objects (saved as <id>_sdf.npy); marching cubes then runs on the device on each decoded grid and the mesh is
 written as <id>.ply next to the pose <id>.npy -- the files the reference's extract_map_objects.py:46-63 produces.
 
-    python tools/remesh_map.py --config configs/config_kitti.json --map_dir map/kitti/07 [--voxels_dim 64]
+    python tools/remesh_map.py --config configs/config_kitti.json --map_dir map/kitti/07 [--voxels_dim 64] [--prepass f16]
+
+--prepass f16|bf16 meshes the whole map in one batched call instead (dsp_extract_meshes: low-precision prepass over the grids, fp32
+only in the surface band; the same meshes, bit for bit) and writes no <id>_sdf.npy, since those volumes are not fp32 away from the
+surface.
 """
 import argparse
 import os
@@ -22,17 +26,40 @@ def main():
     ap.add_argument("--config", required=True)
     ap.add_argument("--map_dir", required=True)
     ap.add_argument("--voxels_dim", type=int, default=64)
+    ap.add_argument("--prepass", choices=("off", "f16", "bf16"), default="off",
+                    help="off (default): decode every grid in fp32, save it as <id>_sdf.npy, mesh it.  f16 / bf16: mesh all objects in one "
+                         "batched call with the low-precision prepass (fp32 only in the surface band; identical meshes); no <id>_sdf.npy is "
+                         "written, because those volumes are not fp32 away from the surface")
     args = ap.parse_args()
     from reconstruct.utils import get_configs, get_decoder, write_mesh_to_ply, convert_sdf_voxels_to_mesh
     from reconstruct.optimizer import MeshExtractor
     from dsp_slam_amd.map_objects import read_map_objects
     cfg = get_configs(args.config)
     objs = read_map_objects(os.path.join(args.map_dir, "MapObjects.txt"))
+    save_dir = os.path.join(args.map_dir, "objects")
+    if args.prepass != "off":
+        ext = MeshExtractor(get_decoder(cfg), cfg.optimizer.code_len, args.voxels_dim, prepass=args.prepass)
+        t0 = time.time()
+        meshes = ext.extract_meshes_from_codes([o["code"] for o in objs])
+        st = ext.decoder.engine.mesh_stats()
+        print("meshed %d grids of %d^3 in %.3f s (%s prepass: %.2f %% of the grid points in fp32, %d objects re-run in fp32)" % (
+            len(objs), args.voxels_dim, time.time() - t0, args.prepass,
+            100.0 * (st["band_points"] + st["audit_points"] + st["dense_points"]) / max(1, st["prepass_points"]), st["reruns"]))
+        os.makedirs(save_dir, exist_ok=True)
+        n_ok = 0
+        for o, m in zip(objs, meshes):
+            np.save(os.path.join(save_dir, "%d.npy" % o["id"]), o["pose"])
+            if m.vertices.shape[0] == 0:
+                print("object %d: Surface level must be within volume data range." % o["id"])
+                continue
+            write_mesh_to_ply(m.vertices, m.faces, os.path.join(save_dir, "%d.ply" % o["id"]))
+            n_ok += 1
+        print("wrote %d meshes" % n_ok)
+        return
     ext = MeshExtractor(get_decoder(cfg), cfg.optimizer.code_len, args.voxels_dim)
     t0 = time.time()
     grids = ext.decode_grids([o["code"] for o in objs])
     print("decoded %d grids of %d^3 in %.3f s" % (len(objs), args.voxels_dim, time.time() - t0))
-    save_dir = os.path.join(args.map_dir, "objects")
     os.makedirs(save_dir, exist_ok=True)
     for o, g in zip(objs, grids):
         np.save(os.path.join(save_dir, "%d.npy" % o["id"]), o["pose"])

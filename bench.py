@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Benchmark of the DeepSDF shape/pose Gauss-Newton hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 5 --warmup 1 [--config cfg2x64|cfg4|cfg5] [--prepass auto|off|f16|bf16] [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--config cfg2x64|cfg4|cfg5] [--prepass auto|off|f16|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one pass of the hot path (Optimizer.reconstruct_object, every GN iteration) over one batch of synthetic
 objects per GPU, inputs already resident in HBM (dsp_batch_create uploads them before the timed region), followed by one
@@ -23,25 +23,36 @@ object order, as Batch.results() hands them to a caller -- to DIR/t_cam_obj.npy 
 32 columns), DIR/loss.npy (N,) and DIR/status.npy (N,; 0 = good), all float32.  The inputs are seeded, so two builds run with the same
 arguments can be compared output for output.
 
-The JSON line also carries
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write --dump-outputs, print the JSON line.  Besides
+`value`, `ms_per_step` and `dtype` that line carries what the headline's own steps measured (HIP events around every decoder launch):
   roofline      fp32-MFMA roofline of the dominant fp32 kernel (forward decoder with relu-mask export, mlp_kernel<1>):
                 algorithmic FLOPs = points the launches actually decode x 3 671 040 FLOP / HIP-event time
                 of those launches;
   prepass       the low-precision classification kernel in front of it (mlp_lp_kernel, f16 MFMA), priced SEPARATELY
                 against the dense 16-bit MFMA peak -- never mixed into the fp32 fraction;
+  by_rank       every rank's own fractions, guard counters, sum of V and K, per-kernel ms.
+
+--full adds, after the headline leg and in this order, the legs that take runs of their own (--no-prepass-off, --no-lp, --no-cpu-baseline
+and --latency-runs trim them; a plain run ignores those four):
   prepass_off   the same batch timed in the same run, over the same number of steps, with the prepass OFF (every in-sphere sample through
                 the fp32 kernel, as the reference evaluates it): objects/s (= the top-level `value_fp32_only`), ms_per_step and the fp32
                 kernel's roofline fraction of THAT run; `dtype` says what the headline computed in ("f32 + f16 classifier");
-  roofline.rocprof_check
-                per LEG of this process (headline warm-up / timed, prepass-off warm-up / timed, clock probe, latency probes): launch
-                counts and HIP-event averages of the decoder kernels.  Every leg opens with one launch of a marker kernel (k_debug_lie), so
-                tools/rocpd_legs.py can split a rocprofv3 kernel trace of the same command at the marker dispatches and compare each
-                population of a kernel with its own figure (profiles/rNN_kernel_stats.md);
+  lp_compute    the same batch in the opt-in low-precision compute mode (16-bit MFMA operands, fp32 accumulation) over as many steps: its
+                objects/s (= the top-level `value_lp`), rooflines, and how far its results sit from the fp32 path's (cfg2x64 only);
+  prepass.sustained_clock_mhz
+                the shader clock granted under a bare prepass decode (also by_rank[].prepass_clock_mhz; null in a plain run);
+  latency_ms_p50, latency_kitti_size_ms_p50, latency_one_shot_ms_p50, pose_only
+                one-object latencies and the pose-only batch (N=1, cfg2x64 only);
   cpu_baseline  the reference itself (kind "reference") when DSP_REFERENCE_ROOT points at a DSP-SLAM checkout, else
                 oracle/torch_baseline.py (kind "port", `port` = "torch-restatement": the reference's own torch op sequence written out, bit-identical
                 results; `calibrated_vs_reference` = its time / the unmodified reference's, measured in the build container,
                 profiles/cpu_baseline_calibration.json), timed on this box's host cores on one warm-up + THREE cfg2 objects (rank 0, N=1 only;
                 objects/s = 1 / mean, p50 alongside: BASELINE.md section 2) -- a reported baseline, not a target.
+
+roofline.rocprof_check lists per LEG of this process (headline warm-up / timed, then the legs --full adds) the launch counts and HIP-event
+averages of the decoder kernels.  Every leg opens with one launch of a marker kernel (k_debug_lie), so tools/rocpd_legs.py can split a
+rocprofv3 kernel trace of the same command at the marker dispatches and compare each population of a kernel with its own figure
+(profiles/rNN_kernel_stats.md).
 """
 import argparse
 import json
@@ -120,7 +131,7 @@ def dump_outputs(out_dir, packed, D):
         np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -136,9 +147,15 @@ def main():
     ap.add_argument("--latency-runs", type=int, default=9)
     ap.add_argument("--serial-batches", action="store_true")     # cfg5: run the two decoders' batches back to back from one host thread (round 5's form)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None)  # the last timed step's results as DIR/<name>.npy (module docstring)
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true")                # also run every leg beyond the headline (module docstring)
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -331,7 +348,7 @@ def main():
         dump_outputs(args.dump_outputs, gathered[0], D)
     # the same batch with the prepass OFF, timed in the same run (every rank takes part: the steps contain the collective)
     off_run = None
-    if args.config == "cfg2x64" and int(acc.get("prepass_mode", 0)) != 0 and not args.no_prepass_off:
+    if args.full and args.config == "cfg2x64" and int(acc.get("prepass_mode", 0)) != 0 and not args.no_prepass_off:
         for bt in batches:
             bt.set_prepass(0)
         off_steps = max(1, args.steps)        # the strict reference-precision leg is timed over as many steps as the headline
@@ -343,7 +360,7 @@ def main():
     # the same batch in the OPT-IN low-precision compute mode (dsp_batch_set_compute(F16): 16-bit MFMA operands, fp32 accumulation, everywhere in
     # the decoder -- a non-parity fast path, reported separately and never mixed into the fp32 figures), timed in the same run
     lp_run = None
-    if args.config == "cfg2x64" and not args.no_lp:
+    if args.full and args.config == "cfg2x64" and not args.no_lp:
         try:
             for bt in batches:
                 bt.set_compute(1)
@@ -385,8 +402,10 @@ def main():
     def rate(pts, flop, ms):
         return pts * flop / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
 
-    mark("clock_probe")
-    my_clock = rank_clock_mhz() if int(acc.get("prepass_mode", 0)) else 0.0
+    my_clock = 0.0
+    if args.full:
+        mark("clock_probe")
+        my_clock = rank_clock_mhz() if int(acc.get("prepass_mode", 0)) else 0.0
     mine_rec = [rate(acc["n_fwd_points"], F_FWD, acc["ms_mlp_fwd"]),
                 (acc["n_jac_points"] * F_JAC + acc["n_render_rows"] * (F_JAC - F_FWD)) / (acc["ms_mlp_jac"] * 1e-3) / 1e12 if acc["ms_mlp_jac"] > 0 else 0.0,
                 rate(acc["n_prepass_points"], F_FWD, acc["ms_mlp_prepass"]), my_clock, acc.get("prepass_guard_trips", 0.0),
@@ -439,10 +458,11 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,          # False: the headline leg alone; True: every leg of the module docstring
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "ms_per_step_by_rank": [round(x / args.steps * 1e3, 3) for x in per_rank_s],
         "by_rank": [{"rank": r, "fwd_fp32_frac": round(x[0] / PEAK_FP32_MFMA_TFLOPS, 4), "jac_fp32_frac": round(x[1] / PEAK_FP32_MFMA_TFLOPS, 4),
-                     "prepass_tflops": round(x[2], 1), "prepass_clock_mhz": round(x[3]), "guard_trips": x[4], "guard_reruns": x[5],
+                     "prepass_tflops": round(x[2], 1), "prepass_clock_mhz": round(x[3]) if x[3] > 0 else None, "guard_trips": x[4], "guard_reruns": x[5],
                      "guard_max_err": x[6], "objects_good": int(x[7]), "objects": int(x[8]), "sum_V_per_step": round(x[9]), "sum_K_per_step": round(x[10]),
                      "ms_per_step_by_kernel": {"fwd_fp32": round(x[11], 2), "jacobian_fp32": round(x[12], 2), "prepass": round(x[13], 2)}}
                     for r, x in enumerate(all_recs)],
@@ -452,7 +472,7 @@ def main():
         # what computed: every result-bearing value in fp32 (v_mfma_f32_16x16x4_f32); with the prepass on, an f16 MFMA kernel additionally
         # CLASSIFIES ray samples whose occupancy is exactly 0 or 1 (results bit-identical to the fp32-only run, value_fp32_only below)
         "dtype": "f32 + f16 classifier" if mode == 1 else ("f32 + bf16 classifier" if mode == 2 else "f32"),
-        "value_fp32_only": None,      # objects/s of the same batch with the prepass off (every sample the reference decodes, decoded in fp32): filled below
+        "value_fp32_only": None,      # objects/s of the same batch with the prepass off (every sample the reference decodes, decoded in fp32): filled below (with the prepass on: --full only)
         "data": "synthetic (seeded rounded-box objects, decoder fixture fitted to them; no real weights/datasets offline)",
         "config": {
             "workload": workload,
@@ -579,7 +599,7 @@ def main():
         result["lp_compute"] = lp_block
         result["value_lp"] = lp_block["value"]
 
-    if world == 1 and args.config == "cfg2x64":
+    if args.full and world == 1 and args.config == "cfg2x64":
         # single-object latency (ms/object p50): batch of ONE cfg2 object
         o = objs[0]
         one = eng.batch(prm, [o["t_cam_obj_init"]], [o["pts"]], [o["rays"]], [o["depth"]])
@@ -661,7 +681,7 @@ def main():
         except Exception as e:      # never lose the headline line over the secondary figure
             result["pose_only"] = {"error": repr(e)}
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # checker / baseline code only -- never on the product path
         from oracle import dsp_oracle as O, torch_baseline as TB
         oprm = O.GNParams(**(dict(k1=10.0, k2=100.0, k3=2.5, k4=0.0, b1=0.2, b2=0.02, lr=1.0, s_damp=100.0, num_iterations=5) if args.config == "cfg5" else {}))

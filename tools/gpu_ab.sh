@@ -8,7 +8,7 @@ cd $R
 for v in main "$@"; do
   if [ $v = main ]; then unset DSPGN_LIB; else export DSPGN_LIB=$R/dsp_slam_amd/lib/libdspgn_$v.so; fi
   timeout 300 python -m pytest tests/test_gpu_prepass.py -m gpu -q -k "every_mode or 64_cfg2 or without_the_audit or guard_fires" > $OUT/tests_$v.log 2>&1; tail -2 $OUT/tests_$v.log
-  timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --latency-runs 3 --no-prepass-off 2> $OUT/bench_$v.err | tail -1 > $OUT/bench_$v.json
+  timeout 300 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --latency-runs 3 --no-prepass-off 2> $OUT/bench_$v.err | tail -1 > $OUT/bench_$v.json
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_$v.json"))

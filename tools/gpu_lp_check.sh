@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/${1:-lp}
 mkdir -p $OUT
 cd $R
 timeout 900 python -m pytest tests/test_gpu_lp_compute.py tests/test_gpu_errors.py -q -m gpu -x > $OUT/lp_tests.log 2>&1; echo "lp tests rc=$?"; tail -3 $OUT/lp_tests.log
-timeout 900 python bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 20 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 r = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])

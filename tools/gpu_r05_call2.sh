@@ -18,7 +18,7 @@ cat $OUT/k1_ablation.md
 timeout 600 python -m pytest tests/test_gpu_round4.py tests/test_gpu_cotenant.py --maxfail=10 -q -m gpu -s -k "cluster or cotenant" > $OUT/cluster_tests.log 2>&1; echo "cluster tests rc=$?"
 grep -E "narrow decoder|lost hand-off|co-tenant|passed|failed|Error|assert" $OUT/cluster_tests.log | head -30
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace -d /tmp/prof_legs -o legs -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --latency-runs 1 > $OUT/bench_under_rocprof.txt 2>&1; echo "rocprof rc=$?"
+timeout 400 rocprofv3 --kernel-trace -d $TMPDIR/prof_legs -o legs -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --latency-runs 1 > $OUT/bench_under_rocprof.txt 2>&1; echo "rocprof rc=$?"
 DB=$(find /tmp/prof_legs -name "*.db" | head -1)
 python $R/tools/rocpd_legs.py $DB $OUT/bench_under_rocprof.txt $OUT/legs.md > /dev/null 2>$OUT/legs.err; tail -3 $OUT/legs.err; cat $OUT/legs.md | head -60
 cd $R

@@ -61,7 +61,7 @@ def table_only(name):
 def main():
     b, b4, b5 = bench("bench.json"), bench("bench_cfg4.json"), bench("bench_cfg5.json")
     boff = bench("bench_prepass_off.json") if os.path.exists(os.path.join(SRC, "bench_prepass_off.json")) else None
-    cmd = "python bench.py --steps %d --warmup %d" % (b["steps"], b["warmup"])
+    cmd = "python bench.py --steps %d --warmup %d --full" % (b["steps"], b["warmup"])
 
     # ---- bench lines -------------------------------------------------------------------------------------------------------------
     def row(label, d):
@@ -69,7 +69,7 @@ def main():
         return "| %s | %.1f | %.1f | %.3f | %.3f | %s |" % (label, d["value"], d["ms_per_step"], r["frac"], r["jac_kernel_frac"],
                                                          "%.0f (%.3f)" % (p["achieved"], p["frac"]) if p else "-")
     lines = ["# Round %s -- bench lines" % ROUND + " as printed on an MI355X (one gpurun call, `tools/run_profiles.sh`; this file by `tools/make_profiles.py`)",
-             "", "`%s [--config ...]` (cfg2x64: the driver's own command)" % cmd, "",
+             "", "`%s [--config ...]` (cfg2x64: the benchmark's headline command with every leg)" % cmd, "",
              "| config | objects/s | ms per step | fp32 forward kernel frac of 157.3 TFLOP/s | jacobian kernels frac | prepass kernel TFLOP/s (frac of 2500) |", "|---|---|---|---|---|---|",
              row("cfg2x64 (dtype `%s`)" % b["dtype"], b)]
     if "prepass_off" in b:
@@ -100,7 +100,7 @@ def main():
     lp = b["prepass"]
     pts_per_launch = r["alg_flop_per_launch"] / F_FWD
     prof = bench("bench_under_rocprof_full.txt")
-    text = ["# Round %s -- rocprofv3 kernel trace of the driver's bench command, leg by leg" % ROUND, "",
+    text = ["# Round %s -- rocprofv3 kernel trace of the bench command with every leg, leg by leg" % ROUND, "",
             "`cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -- %s`" % cmd,
             "(64 cfg2 objects per step; every leg of the process opens with one dispatch of the marker kernel `k_debug_lie`: headline warm-up / timed,",
             "prepass-off warm-up / timed, clock probe, three latency probes, pose-only).  Tables by `tools/rocpd_legs.py` and `tools/rocpd_stats.py`, this file by",
@@ -144,7 +144,7 @@ def main():
     wave0 = ld[(K0, "SQ_ACTIVE_INST_ANY")][1] + 0.0
     txt = ["# Round %s -- rocprofv3 PMC passes" % ROUND + " at the bench configuration", "",
            "Four separate `--pmc` passes (no `--stats`, no tracing; one counter group per run) over",
-           "`python bench.py --steps 1 --warmup 1 --no-cpu-baseline --latency-runs 1` -- **64 objects per GPU, the bench configuration** (round 1's pass was",
+           "`python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --latency-runs 1 --no-prepass-off` -- **64 objects per GPU, the bench configuration** (round 1's pass was",
            "taken at 32).  The tables hold the HEADLINE LEG only (`tools/rocpd_pmc.py ... --between 1 3`: the dispatches between bench.py's first and third marker): 2 steps = %d launches of the fp32 forward kernel `mlp_kernel<1>`, %d of the prepass kernel." % (n1, dm[K0][0]),
            "Tables by `tools/rocpd_pmc.py` (kernels matching `mlp_`), this file by `tools/make_profiles.py`.", "",
            "## FETCH_SIZE (KiB)", "", table_only("pmc_fetch.md"), "", "## WRITE_SIZE (KiB)", "", table_only("pmc_write.md"), "",

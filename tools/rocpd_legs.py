@@ -3,7 +3,7 @@
 
     python tools/rocpd_legs.py <results.db> <file holding the bench output> [out.md]
 
-bench.py opens every leg of its run (headline warm-up / timed, prepass-off warm-up / timed, clock probe, latency probes, ...) with one launch
+bench.py opens every leg of its run (headline warm-up / timed; with --full also prepass-off, clock probe, latency probes, ...) with one launch
 of a marker kernel nothing else runs (`k_debug_lie`), and reports per leg the launch count and HIP-event average of the decoder kernels
 (`roofline.rocprof_check.legs`).  This tool splits the trace's dispatches at the marker dispatches and prints, per leg and decoder kernel,
 calls / average / min / max from the TRACE next to the JSON figure and their difference -- so that each population of a kernel (one launch

@@ -83,6 +83,7 @@ SYMBOLS = [
     ("dsp_estimate_pose_batch", C.c_int, [_VP, C.POINTER(GnParams), C.c_int32, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p]),
     ("dsp_batch_create", C.c_int, [_VP, C.POINTER(GnParams), C.c_int32, c_i64p, c_f32p, c_i64p, c_f32p, c_i64p, c_f32p,
                                    c_f32p, c_f32p, C.POINTER(_VP)]),
+    ("dsp_batch_create_pose", C.c_int, [_VP, C.POINTER(GnParams), C.c_int32, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(_VP)]),
     ("dsp_batch_run", C.c_int, [_VP]),
     ("dsp_batch_results", C.c_int, [_VP, c_f32p, c_f32p, c_f32p, c_i32p]),
     ("dsp_batch_stats", C.c_int, [_VP, C.POINTER(Stats)]),

@@ -146,7 +146,7 @@ __global__ void k_init_state(ObjState* st, const float* t_cam_obj, const float* 
     }
     double tco[16], toc[16];
     for (int i = 0; i < 16; ++i) tco[i] = (double)t_cam_obj[16 * b + i];
-    if (pose_only & 1) {   // optimizer.py:52-55: R *= scale before inverting
+    if ((pose_only & 1) && !(pose_only & 2)) {   // optimizer.py:52-55: R *= scale before inverting (an injected start state has it already)
         const double sc = (double)scale_in[b];
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) tco[4 * r + c] = (double)(float)(tco[4 * r + c] * sc);
     }
@@ -1313,7 +1313,13 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     } else {
         // pose-only (optimizer.py:68-72): H = J6^T J6 / M + 1e-2 I, b = -J6^T r / M with the raw residual
         const int Ma = (s.n_alive >= 0) ? s.n_alive : M;
-        if (Ma == 0) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }
+        if (Ma == 0) {      // no point (left): H = J^T J / 0 is NaN in the reference; the trace still records the count
+            if (tid == 0) {
+                s.status = DSP_STATUS_NAN;
+                if (trace) trace[((size_t)iter * n_obj + b) * TRACE_STRIDE + NSOLVE * NSOLVE + 2 * NSOLVE + 82] = 0.f;
+            }
+            return;
+        }
         for (int e = tid; e < n * (n + 1); e += SOLVE_THREADS) {
             const int i = e / (n + 1), j = e % (n + 1);
             double v;
@@ -1333,7 +1339,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         if (tid == 0) {
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 80] = (float)s.V;
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 81] = (float)s.m;
-            tr[NSOLVE * NSOLVE + 2 * NSOLVE + 82] = (float)s.K;
+            // pose-only: K = the points the system was built from (M, or the inlier filter's survivors: Ma above)
+            tr[NSOLVE * NSOLVE + 2 * NSOLVE + 82] = prm.pose_only ? (float)(s.n_alive >= 0 ? s.n_alive : M) : (float)s.K;
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 83] = (float)(s.vsum & 0xffffu);
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 84] = (float)(s.vsum >> 16);
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 85] = (float)(s.ksum & 0xffffu);
@@ -1582,6 +1589,8 @@ __global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int p
     double toc[16], tco[16];
     for (int i = 0; i < 16; ++i) toc[i] = (double)s.t_oc[i];
     if (!inv4(toc, tco)) for (int i = 0; i < 16; ++i) tco[i] = nan("");
+    // pose-only with no point left (J^T J / 0, optimizer.py:69-72): the reference's pose is NaN from then on, and so is this one
+    if (pose_only && s.status == DSP_STATUS_NAN) for (int i = 0; i < 16; ++i) tco[i] = nan("");
     float* row = out_packed + (size_t)DSP_RESULT_WIDTH_DEV * b;
     for (int i = 0; i < 16; ++i) {
         float v = (float)tco[i];

@@ -45,9 +45,15 @@ def _ragged(arrays, width):
 class Batch(object):
     """Device-resident batch of objects (dsp_batch_*): upload once, run many times."""
 
-    def __init__(self, engine, prm, t_cam_obj, pts, rays, depth, codes=None, trace=False):
+    def __init__(self, engine, prm, t_cam_obj, pts, rays, depth, codes=None, trace=False, scale=None):
         self.engine = engine
         self.n = len(pts)
+        self.pose_only = scale is not None
+        if self.pose_only:       # Engine.pose_batch: t_cam_obj holds the SE(3) estimates, rays / depth are unused
+            self._create_pose(prm, t_cam_obj, pts, scale, codes)
+            if trace:
+                L.check(L.load().dsp_batch_enable_trace(self._h, 1), engine._h, "dsp_batch_enable_trace")
+            return
         self._keep = (
             _ragged(pts, 3), _ragged(rays, 3), _ragged(depth, 0),
             L.f32(np.stack([np.asarray(t, np.float32).reshape(4, 4) for t in t_cam_obj])),
@@ -63,6 +69,19 @@ class Batch(object):
         engine._batches.add(self)          # Engine.close() closes its live batches first: a batch must not outlive its handle
         if trace:
             L.check(lib.dsp_batch_enable_trace(self._h, 1), engine._h, "dsp_batch_enable_trace")
+
+    def _create_pose(self, prm, t_co_se3, pts, scale, codes):
+        n = self.n
+        po, p = _ragged(pts, 3)
+        t = L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_co_se3]))
+        sc = L.f32(np.asarray(scale, np.float32).reshape(n))
+        cd = L.f32(np.stack([L.code64(c) for c in codes]))
+        self._keep = (po, p, t, sc, cd)
+        self._h = C.c_void_p()
+        L.check(L.load().dsp_batch_create_pose(self.engine._h, C.byref(prm), n, L.ptr(po, L.c_i64p), L.ptr(p), L.ptr(t), L.ptr(sc), L.ptr(cd),
+                                               C.byref(self._h)), self.engine._h, "dsp_batch_create_pose")
+        self.iters = prm.pose_only_iterations
+        self.engine._batches.add(self)
 
     # ---- the five settings of the C ABI (include/dsp_gn.h) ------------------------------------------------------------------------------
     def set_ray_passes(self, n):
@@ -209,8 +228,10 @@ class Batch(object):
         return {k: getattr(s, k) for k, _ in L.Stats._fields_}
 
     def trace(self, iteration):
+        """One iteration of the last run.  Pose-only batches: H (n, 6, 6), b / dx (n, 6), K = the points the system was built from."""
         n = self.n
-        out = dict(H=np.zeros((n, 71, 71), np.float32), b=np.zeros((n, 71), np.float32), dx=np.zeros((n, 71), np.float32),
+        u = 6 if self.pose_only else 71
+        out = dict(H=np.zeros((n, u, u), np.float32), b=np.zeros((n, u), np.float32), dx=np.zeros((n, u), np.float32),
                    V=np.zeros(n, np.int64), m=np.zeros(n, np.int64), K=np.zeros(n, np.int64),
                    t_obj_cam=np.zeros((n, 4, 4), np.float32), code=np.zeros((n, L.CODE_LEN), np.float32),
                    set_sums=np.zeros((n, 2), np.uint32), depths=np.zeros((n, 64), np.float32))
@@ -500,6 +521,11 @@ class Engine(object):
 
     def batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, trace=False):
         return Batch(self, prm, t_cam_obj, pts, rays, depth, codes, trace)
+
+    def pose_batch(self, prm, t_co_se3, scale, pts, codes, trace=False):
+        """The pose-only batch of estimate_pose_batch, device-resident (dsp_batch_create_pose): run / results / set_iterations / trace /
+        set_start_state(t_obj_cam) work on it; results()[0] is estimate_pose_batch's output, bit for bit."""
+        return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
     def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute)."""

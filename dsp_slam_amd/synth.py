@@ -173,13 +173,19 @@ def _ray_hits_shape(o, d, code3, n_steps=96, half=None):
 
 
 def make_object(seed, n_surface=2000, n_background=500, code_len=64,
-                t_noise=0.25, yaw_noise_deg=5.0, half=None, shape="box"):
+                t_noise=0.25, yaw_noise_deg=5.0, half=None, shape="box", n_foreground=None):
     """One synthetic detection.
 
     Returns a dict with float32 arrays, laid out as the reference's callers build them
     (reconstruct_frame.py:48-57, src/LocalMapping_util.cc:179-180):
       t_cam_obj_gt / t_cam_obj_init (4,4) Sim(3) object->camera, pts (M,3) camera frame,
       rays (M+B,3) with z=1 (foreground rows first), depth (M,), code_gt (code_len,).
+
+    n_foreground=None: the KITTI layout above, one foreground ray per surface point (n_fg == M).
+    n_foreground=k (k >= 0): the monocular layout (src/LocalMapping_util.cc:330-392), where the
+    foreground rays are feature rays of their own: k camera-facing surface points drawn from a
+    separate seeded stream, independent of the M surface points, give rays (k+B,3) and depth (k,).
+    Everything else -- pts, the background rays, both poses -- is what n_foreground=None returns.
     """
     rng = np.random.default_rng(1000 + seed)
     code_gt = np.zeros(code_len)
@@ -211,7 +217,7 @@ def make_object(seed, n_surface=2000, n_background=500, code_len=64,
     depth = pts_c[:, 2].copy()
     fg_rays = pts_c / pts_c[:, 2:3]
 
-    # background rays: uniform in the foreground pixel box (+margin), rejected if they hit the shape
+    # background rays: uniform in the surface points' pixel box (+margin), rejected if they hit the shape
     lo = fg_rays[:, :2].min(0) - 0.05
     hi = fg_rays[:, :2].max(0) + 0.05
     bg = np.zeros((0, 3))
@@ -225,6 +231,20 @@ def make_object(seed, n_surface=2000, n_background=500, code_len=64,
         if n_background == 0:
             break
     bg = bg[:n_background]
+    if n_foreground is not None:
+        n_foreground = int(n_foreground)
+        if n_foreground < 0:
+            raise ValueError("n_foreground must be >= 0")
+        rng_fg = np.random.default_rng(3000 + seed)        # its own stream: the main one, hence pts / background / poses, is untouched
+        fg_o = np.zeros((0, 3))
+        while fg_o.shape[0] < n_foreground:
+            cand = surface_points(sh or code_gt[:3], 4 * n_foreground, rng_fg, half)
+            nrm = _sdf_normal(cand, sh or code_gt[:3], half=half)
+            vis = np.einsum("ij,ij->i", nrm, cam_o[None, :] - cand) > 0.05
+            fg_o = np.concatenate([fg_o, cand[vis]], axis=0)
+        fg_c = fg_o[:n_foreground] @ (scale * r_co).T + t
+        depth = fg_c[:, 2].copy()
+        fg_rays = fg_c / fg_c[:, 2:3]
     rays = np.concatenate([fg_rays, bg], axis=0)
 
     # perturbed initial pose

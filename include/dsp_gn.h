@@ -188,7 +188,10 @@ int dsp_reconstruct_batch(dsp_handle* h, const dsp_gn_params* prm, int32_t n_obj
 
 /* Optimizer.estimate_pose_cam_obj for a ragged batch -- reconstruct/optimizer.py:45-86.
  * t_co_se3_in[i] (4x4 SE(3)), scale[i], pts as above, codes[i] (64).  Output t_co_se3_out[i] (4x4 SE(3)).
- * The inputs are not modified (the reference scales the caller's matrix in place, :53-54). */
+ * The inputs are not modified (the reference scales the caller's matrix in place, :53-54).
+ * After the update of iteration 4 the points with |sdf| > 0.05 at that iteration's start are dropped, and the following iterations
+ * divide by the number left (:76-78).  An object left with no points -- or given none -- has H = J^T J / 0 in the reference, which
+ * returns NaN: such an object's t_co_se3_out is NaN in all 16 entries here too (its status, with dsp_batch_create_pose, is DSP_OBJ_NAN). */
 int dsp_estimate_pose_batch(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                             const float* pts, const float* t_co_se3_in, const float* scale, const float* codes,
                             float* t_co_se3_out);
@@ -241,6 +244,11 @@ int dsp_mesh_fetch(dsp_handle* h, float* vertices, int64_t n_vertices, int32_t* 
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,
                      const float* depth, const float* t_cam_obj_in, const float* codes_in, dsp_batch** out);
+/* The pose-only batch of dsp_estimate_pose_batch (same inputs), device-resident: dsp_batch_run / _results / _set_iterations (the
+ * pose-only iteration count) / _enable_trace / _trace / _debug_start_state / _destroy work on it; dsp_batch_results' t_cam_obj_out is
+ * dsp_estimate_pose_batch's t_co_se3_out, bit for bit; its codes are the input codes and its loss is 0. */
+int dsp_batch_create_pose(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off, const float* pts,
+                          const float* t_co_se3_in, const float* scale, const float* codes, dsp_batch** out);
 int dsp_batch_run(dsp_batch* b);        /* resets the state to the uploaded initial estimate, runs, synchronises */
 int dsp_batch_results(dsp_batch* b, float* t_cam_obj_out, float* codes_out, float* loss_out, int32_t* status_out);
 int dsp_batch_stats(dsp_batch* b, dsp_stats* out);
@@ -324,7 +332,8 @@ int dsp_batch_debug_ray_pass_bounds(dsp_batch* b, const int32_t* bounds, int n_p
  * to the uploaded object->camera estimates.  depths (optional, n_objects x 64, needs t_obj_cam): the FIRST iteration samples the rays at
  * exactly these num_depth_samples depths instead of deriving them from the pose (optimizer.py:120-125) -- the reference derives them in
  * fp32 LAPACK / powf arithmetic that can differ from this library's by 1-2 ulp, which is enough to move samples across the render term's
- * thresholds. */
+ * thresholds.  A pose-only batch (dsp_batch_create_pose) takes t_obj_cam only: the camera->object Sim(3) matrix the reference's
+ * iteration starts from, scale included (optimizer.py:53-55). */
 int dsp_batch_debug_start_state(dsp_batch* b, const float* t_obj_cam, const float* codes, const float* depths);
 /* Forensics: iteration e < n_iterations of the following runs samples the rays at depths[(e * n_objects + i) * 64 ..] instead of
  * the depths derived from the pose (n_iterations = 0 turns the schedule off). */
@@ -353,7 +362,10 @@ int dsp_batch_enable_trace(dsp_batch* b, int on);
 /* Per-iteration trace of the last run (testing): for iteration e < num_iterations and object i,
  * H (71x71), b (71), dx (71), V, m, K, the state the iteration started from, and set_sums[2*i + {0,1}] = order-
  * independent checksums of the in-sphere sample set and of the kept (jacobian) sample set: sum over members of
- * hash(ray << 6 | depth_index), hash(x) = (x * 2654435761) ^ (x >> 7), mod 2^32.  Any pointer may be NULL. */
+ * hash(ray << 6 | depth_index), hash(x) = (x * 2654435761) ^ (x >> 7), mod 2^32.  Any pointer may be NULL.
+ * A pose-only batch (dsp_batch_create_pose) fills H as 6x6 (n_objects x 36), b and dx as 6 per object; its K is the number of points
+ * the iteration's system was built from (M, or those the inlier filter kept after iteration 4), V = m = 0; of an iteration that finds
+ * no point only K (= 0) is written. */
 int dsp_batch_trace(dsp_batch* b, int32_t iteration, float* H, float* bvec, float* dx, int64_t* V, int64_t* m,
                     int64_t* K, float* t_obj_cam, float* code, uint32_t* set_sums, float* depths /* 64 per object */);
 void dsp_batch_destroy(dsp_batch* b);

@@ -729,29 +729,52 @@ def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
                 V=int(vx.shape[0]), K=int(n_k), N=int(n_s), loss=k1 * render_loss + k2 * sdf_loss)
 
 
-def estimate_pose_cam_obj(dec, prm, t_co_se3, scale, pts, code, trace=None):
+def pose_only_system(dec, pts, t_obj_cam, code):
+    """One pose-only linearisation (optimizer.py:62-72) at a camera->object matrix: dict(H (6,6), b (6,), dx (6,), res (N,), n).
+    N = 0 gives what the reference computes for it: 0 / 0 = NaN in H and b, hence in dx."""
+    j7, _, res = compute_sdf_loss(dec, np.asarray(pts, F32), np.asarray(t_obj_cam, F32), np.asarray(code, F32))
+    j6 = j7[:, :6]
+    n = F32(j6.shape[0])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        hess = ((j6.T @ j6) / n).astype(F32) + F32(1e-2) * np.eye(6, dtype=F32)   # :69-70
+        b = (-(j6.T @ res) / n).astype(F32)                                       # :71 raw residual
+    dx = (_inv(hess) @ b).astype(F32) if np.all(np.isfinite(hess)) else np.full(6, np.nan, F32)
+    return dict(H=hess, b=b, dx=dx, res=np.asarray(res, F32).reshape(-1), n=int(j6.shape[0]))
+
+
+POSE_INLIER_TH = F32(0.05)     # optimizer.py:77
+
+
+def estimate_pose_cam_obj(dec, prm, t_co_se3, scale, pts, code, trace=None, states=None):
     """Optimizer.estimate_pose_cam_obj (optimizer.py:45-86) -> (4,4) f32 SE(3) object->camera.
 
     (The reference scales the caller's array in place, :53-54; this restatement works on a copy.)
+    trace (optional list) receives one dict per iteration: the state it started from, H, b, dx, n = the number of points its system was
+    built from, and at e == 4 the residual `res` and the inlier mask `mask` that the filter of :76-78 keeps for the following iterations.
+    An object without points (from the start, or after the filter) gives NaN everywhere, as in the reference.
+    states (tests only): iteration e linearises at states[e] -- a recorded camera->object matrix of the reference -- instead of where
+    the previous update led.
     """
     t_cam_obj = np.asarray(t_co_se3, F32).copy()
     t_cam_obj[:3, :3] *= F32(scale)
     t_obj_cam = _inv(t_cam_obj)
     z = np.asarray(code, F32)
-    pts = np.asarray(pts, F32)
+    pts = np.asarray(pts, F32).reshape(-1, 3)
     for e in range(prm.num_iterations_pose_only):
-        j7, _, res = compute_sdf_loss(dec, pts, t_obj_cam, z)
-        j6 = j7[:, :6]
-        n = F32(j6.shape[0])
-        hess = ((j6.T @ j6) / n).astype(F32) + F32(1e-2) * np.eye(6, dtype=F32)   # :69-70
-        b = (-(j6.T @ res) / n).astype(F32)                                       # :71 raw residual
-        dx = (_inv(hess) @ b).astype(F32)
-        if trace is not None:
-            trace.append(dict(H=hess.copy(), b=b.copy(), dx=dx.copy(), t_obj_cam=t_obj_cam.copy()))
-        t_obj_cam = (exp_se3(dx) @ t_obj_cam).astype(F32)                         # :73-74
-        if e == 4:                                                                # :76-78
-            keep = np.abs(res) <= F32(0.05)
+        if states is not None:
+            t_obj_cam = np.asarray(states[e], F32).copy()
+        it = pose_only_system(dec, pts, t_obj_cam, z)
+        rec = dict(H=it["H"].copy(), b=it["b"].copy(), dx=it["dx"].copy(), t_obj_cam=t_obj_cam.copy(), n=it["n"])
+        with np.errstate(invalid="ignore"):
+            t_obj_cam = (exp_se3(it["dx"]) @ t_obj_cam).astype(F32)                # :73-74
+        if e == 4:                                                                # :76-78: the residual from BEFORE this iteration's update
+            keep = np.abs(it["res"]) <= POSE_INLIER_TH
             pts = pts[keep]
+            rec.update(res=it["res"].copy(), mask=keep)
+        if trace is not None:
+            trace.append(rec)
+    if not np.all(np.isfinite(t_obj_cam)):
+        return np.full((4, 4), np.nan, F32)         # torch.inverse of a NaN matrix: NaN throughout
     out = _inv(t_obj_cam)
     out[:3, :3] /= F32(scale)
     return out

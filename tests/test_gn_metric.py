@@ -61,7 +61,7 @@ def old_max_norm_passes(sys_, it):
 
 # the cfg2-size goldens (cfg2, cfg5, complex) are too slow for the CPU tier here; their recorded states are in the measurement of
 # tools/measure_gn_metric.py that fixed TAU (tests/gn_metric.py)
-SANITY = ["golden_recon_%s.npz" % n for n in ("small", "cfg1", "redwood", "freiburg", "chairs32")]
+SANITY = ["golden_recon_%s.npz" % n for n in ("small", "cfg1", "redwood", "freiburg", "chairs32", "mono_shape", "mono_wide")]
 
 
 @pytest.mark.parametrize("name", SANITY)

@@ -27,7 +27,9 @@ pytestmark = pytest.mark.gpu
 # the last two run on the 32-D chairs decoder; cfg5 is BASELINE configs[4] at full size (4000 surface points + 500 background rays,
 # Redwood hyper-parameters) -- and a fixture on which the reference's OWN 1-ulp spread is below 1e-4 (9.3e-5 pose / 4.4e-5 code)
 CASES = ["golden_recon_small.npz", "golden_recon_cfg1.npz", "golden_recon_redwood.npz", "golden_recon_freiburg.npz", "golden_recon_cfg2.npz",
-         "golden_recon_chairs32.npz", "golden_recon_cfg5.npz"]
+         "golden_recon_chairs32.npz", "golden_recon_cfg5.npz",
+         # the monocular input shape, n_fg != M (src/LocalMapping_util.cc:330-392): n_fg < M with zero-depth foreground rows, and n_fg > M
+         "golden_recon_mono_shape.npz", "golden_recon_mono_wide.npz"]
 # round 5: one cfg2-size object on the decoder fitted to the complex (non-convex, all-64-dims) shape family
 if os.path.exists(os.path.join(ROOT, "tests", "golden", "golden_recon_complex.npz")) and os.path.exists(os.path.join(ROOT, "tests", "golden", "decoder_complex.npz")):
     CASES.append("golden_recon_complex.npz")

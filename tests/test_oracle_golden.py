@@ -83,7 +83,7 @@ def test_huber():
     assert np.isnan(O.get_robust_res(np.zeros(0, np.float32), 0.1)[1])
 
 
-def _check_trace(oracle_decoder, name, tol_final, at_ref_iterations=None, pinned_chain=True, require_final=None):
+def _check_trace(oracle_decoder, name, tol_final, at_ref_iterations=None, pinned_chain=True, require_final=None, depth=None):
     """The oracle against a recorded run of the unmodified reference, in three steps (tests/forensics.py):
     (1) EVERY iteration linearised at the reference's own state and depth samples: identical sets, H / b / dx to 1e-4 (measured ~1e-6);
     (2) all iterations chained, sampling the depths the reference recorded (its float32 torch.inverse / det / pow / linspace chain is
@@ -91,9 +91,11 @@ def _check_trace(oracle_decoder, name, tol_final, at_ref_iterations=None, pinned
         iteration is reached with the states still agreeing to round-off and the samples that switched sets there are named, each
         within round-off of its threshold;
     (3) all iterations chained with the oracle's own depth derivation (what a production run does): bounded by the reference's own
-        spread under 1-ulp input perturbations, with the first flip named the same way."""
+        spread under 1-ulp input perturbations, with the first flip named the same way.
+    depth (fault injection only): the oracle runs on this foreground depth vector instead of the recorded input's."""
     import forensics as F
     g = golden(name)
+    in_depth = g["in_depth"] if depth is None else np.asarray(depth, np.float32)
     n_unk = 7 + oracle_decoder.code_len
     cfg = json.loads(str(g["cfg_json"]))
     prm = O.GNParams.from_configs(cfg)
@@ -104,7 +106,7 @@ def _check_trace(oracle_decoder, name, tol_final, at_ref_iterations=None, pinned
     mask[3:6] = False
     # (1)  (at_ref_iterations: a subset for the full-size fixtures, whose every iteration is covered on the GPU tier)
     for e in (range(n_it) if at_ref_iterations is None else at_ref_iterations):
-        it = F.oracle_linearisation(oracle_decoder, prm, g["in_pts"], g["in_rays"], g["in_depth"], g["it_t_obj_cam"][e], g["it_code"][e], g["it_depths"][e])
+        it = F.oracle_linearisation(oracle_decoder, prm, g["in_pts"], g["in_rays"], in_depth, g["it_t_obj_cam"][e], g["it_code"][e], g["it_depths"][e])
         assert (it["V"], it["K"]) == (int(g["it_V"][e]), int(g["it_K"][e])), "iteration %d: sets differ at the reference's own state" % e
         assert rel(it["H"], g["it_H"][e]) < 1e-4
         # b[3:6] carries k4 * J_rot * res_rot with res_rot = 1 + R_co[1,1]: for a near-upright object that is a difference of two numbers
@@ -121,14 +123,14 @@ def _check_trace(oracle_decoder, name, tol_final, at_ref_iterations=None, pinned
     def chained(depths):
         tr = []
         t0 = None
-        rst = O.reconstruct_object(oracle_decoder, prm, g["in_t_cam_obj_init"], g["in_pts"], g["in_rays"], g["in_depth"], code, trace=tr,
+        rst = O.reconstruct_object(oracle_decoder, prm, g["in_t_cam_obj_init"], g["in_pts"], g["in_rays"], in_depth, code, trace=tr,
                                    t_obj_cam0=t0, sampled_override=depths)
         return rst, tr
 
     def explain_first_flip(tr, first):
         drift = F.state_difference(tr[first]["t_obj_cam"], tr[first]["code"], g["it_t_obj_cam"][first], g["it_code"][first])
         drift = max(drift.values())      # the margins below widen with it: the incoming state difference moves every sample by about that much
-        ref_it = F.oracle_linearisation(oracle_decoder, prm, g["in_pts"], g["in_rays"], g["in_depth"], g["it_t_obj_cam"][first], g["it_code"][first], g["it_depths"][first])
+        ref_it = F.oracle_linearisation(oracle_decoder, prm, g["in_pts"], g["in_rays"], in_depth, g["it_t_obj_cam"][first], g["it_code"][first], g["it_depths"][first])
         dev = F.as_device_grids(F.oracle_grids(tr[first]["sets"], n_rays, n_d))
         flips = F.name_flips(dev[0], dev[1], dev[2], F.oracle_grids(ref_it["sets"], n_rays, n_d), prm.cut_off)
         scale = float(np.cbrt(np.linalg.det(np.linalg.inv(g["it_t_obj_cam"][first].astype(np.float64))[:3, :3])))
@@ -183,6 +185,49 @@ def test_reconstruct_freiburg_hyper_parameters(oracle_decoder):
     """Third hyper-parameter set of the reference (configs/config_freiburg_001.json:15-30: k3 = 0.5, k4 = 0, 5 iterations,
     scale damping 100)."""
     _check_trace(oracle_decoder, "golden_recon_freiburg.npz", 1e-4)
+
+
+@pytest.mark.parametrize("name", ["golden_recon_mono_shape.npz", "golden_recon_mono_wide.npz"])
+def test_reconstruct_monocular_shape(oracle_decoder, name):
+    """The monocular caller's layout (src/LocalMapping_util.cc:330-392): M map points, n_fg != M feature rays with a depth (mono_shape:
+    M = 300, n_fg = 120, its last foreground rows at depth 0 like the caller's zero-initialised depth vector; mono_wide: M = 120,
+    n_fg = 260), Freiburg hyper-parameters, a warm-start code."""
+    g = golden(name)
+    m, n_fg = g["in_pts"].shape[0], g["in_depth"].shape[0]
+    assert n_fg != m and g["in_rays"].shape[0] > max(m, n_fg) and "in_code" in g.files
+    if name == "golden_recon_mono_shape.npz":
+        assert (m, n_fg) == (300, 120) and np.all(g["in_depth"][-6:] == 0) and np.all(g["in_depth"][:-6] > 0)
+    _check_trace(oracle_decoder, name, 1e-4)
+
+
+@pytest.mark.parametrize("name", ["golden_recon_mono_shape.npz", "golden_recon_mono_wide.npz"])
+def test_monocular_check_rejects_a_split_at_M(oracle_decoder, name):
+    """Fault injection: an oracle that splits foreground from background at row M (the number of surface points) instead of n_fg -- rows
+    n_fg .. M-1 read as foreground with the zero-initialised depth 0 when n_fg < M, rows M .. n_fg-1 read as background when n_fg > M.
+    The trace check rejects it on both goldens."""
+    g = golden(name)
+    m = g["in_pts"].shape[0]
+    d = np.concatenate([g["in_depth"], np.zeros(max(0, m - g["in_depth"].shape[0]), np.float32)])[:m]
+    with pytest.raises(AssertionError):
+        _check_trace(oracle_decoder, name, 1e-4, depth=d)
+
+
+def test_synth_n_foreground():
+    """synth.make_object(n_foreground=None) is the layout every existing golden was recorded from, bit for bit; an integer gives that many
+    foreground rays with depths, independent of the surface points, and leaves everything else unchanged."""
+    from dsp_slam_amd import synth
+    g = golden("golden_recon_small.npz")
+    a = synth.make_object(11, n_surface=200, n_background=50)
+    for k in ("pts", "rays", "depth", "t_cam_obj_init", "t_cam_obj_gt", "code_gt"):
+        assert np.array_equal(a[k], g["in_" + k]), k
+    for k in (0, 37, 200, 333):
+        b = synth.make_object(11, n_surface=200, n_background=50, n_foreground=k)
+        assert b["depth"].shape == (k,) and b["rays"].shape == (k + 50, 3) and np.all(b["depth"] > 0)
+        assert np.array_equal(b["rays"][k:], a["rays"][200:])
+        for q in ("pts", "t_cam_obj_init", "t_cam_obj_gt", "code_gt"):
+            assert np.array_equal(b[q], a[q]), q
+    with pytest.raises(ValueError):
+        synth.make_object(11, n_surface=20, n_background=5, n_foreground=-1)
 
 
 def test_reconstruct_cfg1(oracle_decoder):
@@ -324,3 +369,143 @@ def test_lie_goldens_regenerate_bit_for_bit(tmp_path):
     assert sorted(a.files) == sorted(b.files)
     for k in a.files:
         assert np.array_equal(a[k], b[k]), k
+
+
+# ---- pose-only beyond five iterations (golden_pose_only_8it.npz, tools/make_golden.py pose8): the inlier filter after the update of
+#      e == 4 and the changed 1 / M of e >= 5 (optimizer.py:59-78) ------------------------------------------------------------------------
+POSE_TOL = 1e-4
+
+
+def _pose_prm(n_it):
+    return O.GNParams(num_iterations_pose_only=n_it)
+
+
+def _pose_variant(dec, prm, t_co_se3, scale, pts, code, trace=None, states=None, fault=None):
+    """O.estimate_pose_cam_obj with one fault: 'no_filter' (the filter skipped), 'post_update' (filtering on the residual after
+    iteration 4's update), 'keep_1_over_M' (H and b still divided by the original M after filtering), 'filter_at_5' (the filter after
+    e == 5).  fault=None is the oracle itself, bit for bit (checked by the caller)."""
+    F32 = np.float32
+    t_cam_obj = np.asarray(t_co_se3, F32).copy()
+    t_cam_obj[:3, :3] *= F32(scale)
+    t_obj_cam = O._inv(t_cam_obj)
+    pts = np.asarray(pts, F32)
+    m0 = pts.shape[0]
+    for e in range(prm.num_iterations_pose_only):
+        if states is not None:
+            t_obj_cam = np.asarray(states[e], F32).copy()
+        it = O.pose_only_system(dec, pts, t_obj_cam, code)
+        if fault == "keep_1_over_M" and it["n"] != m0:
+            n, n0 = F32(it["n"]), F32(m0)
+            it["H"] = ((it["H"] - F32(1e-2) * np.eye(6, dtype=F32)) * n / n0 + F32(1e-2) * np.eye(6, dtype=F32)).astype(F32)
+            it["b"] = (it["b"] * n / n0).astype(F32)
+            it["dx"] = (O._inv(it["H"]) @ it["b"]).astype(F32)
+        rec = dict(H=it["H"], b=it["b"], dx=it["dx"], t_obj_cam=t_obj_cam.copy(), n=it["n"])
+        t_obj_cam = (O.exp_se3(it["dx"]) @ t_obj_cam).astype(F32)
+        if e == (5 if fault == "filter_at_5" else 4) and fault != "no_filter":
+            res = O.pose_only_system(dec, pts, t_obj_cam, code)["res"] if fault == "post_update" else it["res"]
+            keep = np.abs(res) <= O.POSE_INLIER_TH
+            pts = pts[keep]
+            rec.update(res=res, mask=keep)
+        if trace is not None:
+            trace.append(rec)
+    out = O._inv(t_obj_cam)
+    out[:3, :3] /= F32(scale)
+    return out
+
+
+def _pose_failures(run, g):
+    """What a pose-only program gets wrong against the 8-iteration golden, and by how much it moves H / b at iterations 5-7 and the output
+    (relative).  run(trace, states) -> output.  Two parts:
+      at the reference's recorded states (the whole trajectory injected): the point count of every iteration exactly, the inlier mask of
+      e == 4 exactly, H, b, dx within POSE_TOL relative (measured <= 3e-5);
+      chained from the golden's input: the counts and the mask exactly, every iteration's starting state and the output within POSE_TOL
+      (measured 3e-6).  The chained H / b are not held to POSE_TOL: one state ulp away, a point's ReLU pattern can flip, which moves H by
+      2e-4 at iteration 5 on this golden (printed)."""
+    fails, move = [], 0.0
+    tr = []
+    run(tr, g["it_t_obj_cam"])
+    ns = [t["n"] for t in tr]
+    if ns != list(g["it_n"]):
+        fails.append("counts at the reference's states %s != %s" % (ns, list(g["it_n"])))
+    if len(tr) < 5 or "mask" not in tr[4] or not np.array_equal(tr[4]["mask"], g["mask_e4"]):
+        fails.append("inlier mask of e == 4 differs")
+    for e, t in enumerate(tr):
+        for k in ("H", "b", "dx"):
+            r = rel(t[k], g["it_" + k][e])
+            if not r < POSE_TOL:
+                fails.append("iteration %d: rel d%s %.2e at the reference's state" % (e, k, r))
+            if e >= 5 and k != "dx":
+                move = max(move, r)
+    tr = []
+    out = run(tr, None)
+    if [t["n"] for t in tr] != list(g["it_n"]):
+        fails.append("chained counts %s" % [t["n"] for t in tr])
+    if len(tr) < 5 or "mask" not in tr[4] or not np.array_equal(tr[4]["mask"], g["mask_e4"]):
+        fails.append("chained inlier mask differs")
+    for e, t in enumerate(tr):
+        r = rel(t["t_obj_cam"], g["it_t_obj_cam"][e])
+        if not r < POSE_TOL:
+            fails.append("chained state of iteration %d: rel %.2e" % (e, r))
+    r = rel(out, g["out"])
+    move = max(move, r)
+    if not r < POSE_TOL:
+        fails.append("output: rel %.2e" % r)
+    print("chained rel dH / db by iteration: %s" % ", ".join("%.1e / %.1e" % (rel(t["H"], g["it_H"][e]), rel(t["b"], g["it_b"][e])) for e, t in enumerate(tr)))
+    return fails, move
+
+
+def test_pose_only_golden_margins():
+    """The golden exercises what it is for: >= 10 % planted outliers, the filter really drops points, no residual at e == 4 within 1e-4
+    of the threshold, and at least one point whose keep / drop decision differs when the residual after iteration 4's update is used."""
+    g = golden("golden_pose_only_8it.npz")
+    r4 = g["res_e4"].astype(np.float64)
+    assert g["outlier_idx"].shape[0] >= 0.1 * g["pts"].shape[0]
+    assert np.array_equal(g["mask_e4"], np.abs(g["res_e4"]) <= np.float32(0.05))
+    assert np.abs(np.abs(r4) - 0.05).min() >= 1e-4
+    assert (~g["mask_e4"]).sum() >= 10
+    assert (g["mask_e4"] != g["mask_post_e4"]).sum() >= 1
+    assert list(g["it_n"]) == [300] * 5 + [int(g["mask_e4"].sum())] * 3
+    assert list(g["allout_it_n"][:5]) == [150] * 5 and not g["allout_it_n"][5:].any()
+    assert str(g["allout_error"]) == "" and str(g["empty_error"]) == ""       # the reference raises nothing for either ...
+    assert np.isnan(g["allout_out"]).all() and np.isnan(g["empty_out"]).all()  # ... and returns NaN throughout
+
+
+def test_pose_only_8_iterations_against_the_reference(oracle_decoder):
+    g = golden("golden_pose_only_8it.npz")
+    prm = _pose_prm(8)
+    args = (oracle_decoder, prm, g["t_co_se3"], float(g["scale"]), g["pts"], g["code"])
+    fails, _ = _pose_failures(lambda tr, st: O.estimate_pose_cam_obj(*args, trace=tr, states=st), g)
+    assert not fails, fails
+    for n_it in (5, 6, 10):
+        out = O.estimate_pose_cam_obj(oracle_decoder, _pose_prm(n_it), g["t_co_se3"], float(g["scale"]), g["pts"], g["code"])
+        assert rel(out, g["out_%dit" % n_it]) < POSE_TOL, n_it
+
+
+@pytest.mark.parametrize("fault", ["no_filter", "post_update", "keep_1_over_M", "filter_at_5"])
+def test_pose_only_check_rejects_a_misplaced_filter(oracle_decoder, fault):
+    """Fault injection (the style of tests/test_gn_metric.py): the oracle with one thing of the filter wrong.  Each moves H or b at
+    iterations 5-7, or the output, by more than 10x POSE_TOL, and the check above rejects it.  The variant without a fault IS the oracle."""
+    g = golden("golden_pose_only_8it.npz")
+    prm = _pose_prm(8)
+    args = (oracle_decoder, prm, g["t_co_se3"], float(g["scale"]), g["pts"], g["code"])
+    tr0, tr1 = [], []
+    assert np.array_equal(_pose_variant(*args, trace=tr0), O.estimate_pose_cam_obj(*args, trace=tr1))
+    assert all(np.array_equal(a["H"], b["H"]) and np.array_equal(a["b"], b["b"]) and a["n"] == b["n"] for a, b in zip(tr0, tr1))
+    fails, move = _pose_failures(lambda tr, st: _pose_variant(*args, trace=tr, states=st, fault=fault), g)
+    print(fault, "moves H / b at 5-7 or the output by %.2e relative; rejected for: %s" % (move, "; ".join(fails[:4])))
+    assert move > 10 * POSE_TOL, (fault, move)
+    assert fails, fault
+
+
+def test_pose_only_without_points_is_nan_as_in_the_reference(oracle_decoder):
+    """Every point dropped by the filter, and no points at all: the reference's J^T J / 0 makes its pose NaN (recorded)."""
+    g = golden("golden_pose_only_8it.npz")
+    tr = []
+    out = O.estimate_pose_cam_obj(oracle_decoder, _pose_prm(8), g["allout_t_co_se3"], float(g["allout_scale"]), g["allout_pts"], g["allout_code"], trace=tr)
+    assert [t["n"] for t in tr] == list(g["allout_it_n"])
+    assert np.isnan(out).all() and np.isnan(g["allout_out"]).all()
+    out = O.estimate_pose_cam_obj(oracle_decoder, _pose_prm(8), g["t_co_se3"], float(g["scale"]), np.zeros((0, 3), np.float32), g["code"])
+    assert np.isnan(out).all() and np.isnan(g["empty_out"]).all()
+    # five iterations never reach a filtered system: the all-outlier object then has a finite pose
+    assert np.isfinite(O.estimate_pose_cam_obj(oracle_decoder, _pose_prm(5), g["allout_t_co_se3"], float(g["allout_scale"]), g["allout_pts"],
+                                               g["allout_code"])).all()

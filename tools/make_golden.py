@@ -387,6 +387,147 @@ def main():
         print("pose-only: t-err %.4f -> %.4f" % (np.linalg.norm(t_se3[:3, 3] - gt[:3, 3]),
                                                  np.linalg.norm(rst.numpy()[:3, 3] - gt[:3, 3])))
 
+    # ---- D2. pose-only beyond five iterations: the inlier filter after the update of e == 4 (optimizer.py:76-78) and the changed 1 / M of
+    #          e >= 5; an object whose every point the filter drops, and one with no points at all
+    if want("pose8"):
+        out = pose_only_golden(ropt, decoder, cfg_kitti, tmp, get_configs)
+        np.savez_compressed(os.path.join(GOLD, "golden_pose_only_8it.npz"), **out)
+
+    # ---- E. the monocular input shape (src/LocalMapping_util.cc:330-392): M map points on the object, n_fg != M feature rays with a depth,
+    #         rows of the zero-initialised depth vector that the caller's loop skips keep depth 0 (:355-376)
+    if want("mono_shape"):
+        obj = synth.make_object(51, n_surface=300, n_background=200, n_foreground=120)
+        obj["depth"][-6:] = 0.0
+        code0 = np.zeros(64, np.float32)
+        code0[:3] = obj["code_gt"][:3] * 0.6
+        recon("golden_recon_mono_shape.npz", obj, make_cfg(cars_dir, FREIBURG, "Freiburg"), code=code0)
+    if want("mono_wide"):
+        obj = synth.make_object(52, n_surface=120, n_background=100, n_foreground=260)
+        code0 = np.zeros(64, np.float32)
+        code0[:3] = obj["code_gt"][:3] * 0.6
+        recon("golden_recon_mono_wide.npz", obj, make_cfg(cars_dir, FREIBURG, "Freiburg"), code=code0)
+
+
+POSE_TH = 0.05          # optimizer.py:76
+POSE_MARGIN = 1e-4      # no recorded |r| at e == 4 may lie closer than this to POSE_TH
+
+
+def _pose_inputs(seed, n_pts, n_out, all_out=False):
+    """A pose-only detection with planted outliers: n_out of the n_pts surface points pulled towards the camera along their ray, so far
+    that the residual at e == 4 is well beyond POSE_TH for most of them and near it (on either side) for some.  all_out: n_pts points
+    of which none lies near the surface."""
+    obj = synth.make_object(seed, n_surface=n_pts, n_background=0, t_noise=0.5, yaw_noise_deg=10.0)    # far enough out that e == 4 still moves
+    rng = np.random.default_rng(5000 + seed)
+    s = float(obj["scale"])
+    t_se3 = obj["t_cam_obj_init"].copy()
+    t_se3[:3, :3] /= s
+    code = np.zeros(64, np.float32)
+    code[:3] = obj["code_gt"][:3]
+    pts = obj["pts"].astype(np.float64)
+    if all_out:
+        # no pose can fit these: a shell 1.1 .. 1.4 object units around the object's centre, every point far from any surface
+        u = rng.normal(size=(n_pts, 3))
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        pts = obj["t_cam_obj_gt"][:3, 3].astype(np.float64) + u * (rng.uniform(1.1, 1.4, n_pts) * s)[:, None]
+        return t_se3, np.float32(s), pts.astype(np.float32), code, obj["t_cam_obj_gt"], np.arange(n_pts)
+    idx = rng.choice(n_pts, n_out, replace=False)
+    # object-frame distance: 60 % near the threshold (0.04 .. 0.12), the rest far out (0.2 .. 0.5)
+    d = np.where(rng.uniform(size=idx.shape[0]) < 0.6, rng.uniform(0.04, 0.12, idx.shape[0]), rng.uniform(0.2, 0.5, idx.shape[0]))
+    ray = pts[idx] / np.linalg.norm(pts[idx], axis=1, keepdims=True)
+    pts[idx] -= ray * (d * s)[:, None]
+    return t_se3, np.float32(s), pts.astype(np.float32), code, obj["t_cam_obj_gt"], idx
+
+
+def run_pose(ropt, opt, t_se3, s, pts, code):
+    """Optimizer.estimate_pose_cam_obj with its per-iteration system recorded: the state at the start, H, b, dx, the number of points the
+    system was built from and the raw residuals.  Returns (output or None, the exception's text or None, iterations)."""
+    import torch
+    its = []
+    saved = dict(sdf=ropt.compute_sdf_loss, inv=torch.inverse, mv=torch.mv)
+
+    def w_sdf(decoder, p, t_obj_cam, z):
+        out = saved["sdf"](decoder, p, t_obj_cam, z)
+        its.append(dict(t_obj_cam=t_obj_cam.clone().numpy(), n=int(p.shape[0]), res=out[2].reshape(-1).clone().numpy()))
+        return out
+
+    def w_inv(x):
+        out = saved["inv"](x)
+        if its and x.shape == (6, 6):
+            its[-1]["H"] = x.clone().numpy()
+        return out
+
+    def w_mv(a, b):
+        out = saved["mv"](a, b)
+        if its and a.shape == (6, 6):
+            its[-1]["b"] = b.clone().numpy()
+            its[-1]["dx"] = out.clone().numpy()
+        return out
+
+    ropt.compute_sdf_loss, torch.inverse, torch.mv = w_sdf, w_inv, w_mv
+    try:
+        rst, err = opt.estimate_pose_cam_obj(t_se3.copy(), float(s), pts.copy(), code.copy()).numpy(), None
+    except Exception as e:          # recorded as it is: what the reference does with the input
+        rst, err = None, "%s: %s" % (type(e).__name__, e)
+    finally:
+        ropt.compute_sdf_loss, torch.inverse, torch.mv = saved["sdf"], saved["inv"], saved["mv"]
+    return rst, err, its
+
+
+def pose_only_golden(ropt, decoder, cfg_kitti, tmp, get_configs):
+    import torch
+
+    def optimizer(n_it):
+        c = json.loads(json.dumps(cfg_kitti))
+        c["optimizer"]["pose_only_optim"]["num_iterations"] = n_it
+        with open(os.path.join(tmp, "cfg_pose%d.json" % n_it), "w") as f:
+            json.dump(c, f)
+        return ropt.Optimizer(decoder, get_configs(os.path.join(tmp, "cfg_pose%d.json" % n_it))), c
+
+    opt8, c8 = optimizer(8)
+    for seed in range(60, 400):
+        t_se3, s, pts, code, gt, idx = _pose_inputs(seed, 300, 40)
+        out8, err, its = run_pose(ropt, opt8, t_se3, s, pts, code)
+        assert err is None and len(its) == 8 and all("dx" in it for it in its)
+        r4 = its[4]["res"]
+        keep = np.abs(r4) <= np.float32(POSE_TH)            # the reference's own expression (optimizer.py:77) on its own residual
+        # the residual after iteration 4's update, at the state iteration 5 starts from, for ALL points: what a filter placed one step late sees
+        r_post = ropt.compute_sdf_loss(decoder, torch.from_numpy(pts), torch.from_numpy(its[5]["t_obj_cam"]),
+                                       torch.from_numpy(code))[2].reshape(-1).numpy()
+        keep_post = np.abs(r_post) <= np.float32(POSE_TH)
+        margin = float(np.abs(np.abs(r4.astype(np.float64)) - POSE_TH).min())
+        n_drop, n_moved = int((~keep).sum()), int((keep != keep_post).sum())
+        print("pose8 seed %d: drops %d of %d, margin %.2e, post-update filter changes %d decisions" % (seed, n_drop, pts.shape[0], margin, n_moved))
+        if margin >= POSE_MARGIN and n_moved >= 1 and n_drop >= 30:
+            break
+    else:
+        raise RuntimeError("no seed meets the margins")
+    assert [it["n"] for it in its] == [300] * 5 + [int(keep.sum())] * 3
+    out = dict(seed=np.int64(seed), t_co_se3=t_se3, scale=s, pts=pts, code=code, t_cam_obj_gt=gt, outlier_idx=idx.astype(np.int64),
+               num_iterations=np.int64(8), out=out8, cfg_json=np.array(json.dumps(c8)),
+               it_t_obj_cam=np.stack([it["t_obj_cam"] for it in its]), it_H=np.stack([it["H"] for it in its]),
+               it_b=np.stack([it["b"] for it in its]), it_dx=np.stack([it["dx"] for it in its]),
+               it_n=np.array([it["n"] for it in its], np.int64),
+               res_e4=r4, mask_e4=keep, res_post_e4=r_post, mask_post_e4=keep_post)
+    for n_it in (5, 6, 10):
+        o, err, _ = run_pose(ropt, optimizer(n_it)[0], t_se3, s, pts, code)
+        assert err is None
+        out["out_%dit" % n_it] = o
+    # the ragged companions: every point an outlier (the filter leaves none), and no points at all
+    t_a, s_a, pts_a, code_a, gt_a, _ = _pose_inputs(seed + 1000, 150, 150, all_out=True)
+    o_a, err_a, its_a = run_pose(ropt, opt8, t_a, s_a, pts_a, code_a)
+    assert all(abs(float(r)) > POSE_TH + POSE_MARGIN for r in its_a[4]["res"])
+    out.update(allout_t_co_se3=t_a, allout_scale=s_a, allout_pts=pts_a, allout_code=code_a, allout_it_n=np.array([it["n"] for it in its_a], np.int64),
+               allout_error=np.array(err_a or ""))
+    if o_a is not None:
+        out["allout_out"] = o_a
+    o_e, err_e, its_e = run_pose(ropt, opt8, t_se3, s, np.zeros((0, 3), np.float32), code)
+    out.update(empty_error=np.array(err_e or ""), empty_it_n=np.array([it["n"] for it in its_e], np.int64))
+    if o_e is not None:
+        out["empty_out"] = o_e
+    print("pose8: alive %s, |out - gt| %.4f;  all-outlier: n %s -> %s;  empty -> %s" % (
+        out["it_n"], np.abs(out8[:3, 3] - gt[:3, 3]).max(), out["allout_it_n"], err_a or o_a.tolist(), err_e or o_e.tolist()))
+    return out
+
 
 if __name__ == "__main__":
     main()

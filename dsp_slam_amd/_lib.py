@@ -132,6 +132,8 @@ SYMBOLS = [
     ("dsp_pg_edge_linearize", C.c_int, [C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p]),
     ("dsp_pg_edge_chi2", C.c_int, [C.c_int64, c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     ("dsp_pg_vertex_oplus", C.c_int, [C.c_int64, C.c_int, c_f64p, c_f64p, c_f64p]),
+    # test hook, not in dsp_gn.h: the launch plan of one row of inputs, on the host (tests/test_launch_plan.py)
+    ("dsp_debug_launch_plan", C.c_int, [c_i32p, C.c_int, c_i32p, C.c_int]),
 ]
 
 

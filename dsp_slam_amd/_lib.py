@@ -108,6 +108,11 @@ SYMBOLS = [
     ("dsp_debug_lie", C.c_int, [_VP, C.c_int, c_f32p, C.c_int32, c_f32p]),
     ("dsp_batch_enable_trace", C.c_int, [_VP, C.c_int]),
     ("dsp_batch_trace", C.c_int, [_VP, C.c_int32, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_f32p, c_f32p, C.POINTER(C.c_uint32), c_f32p]),
+    ("dsp_reconstruct_multiview", C.c_int, [_VP, C.POINTER(GnParams), C.c_int32, c_i64p, c_f32p, c_i64p, c_f32p, c_i64p, c_f32p, c_i64p, c_f32p,
+                                            c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p]),
+    ("dsp_batch_create_multiview", C.c_int, [_VP, C.POINTER(GnParams), C.c_int32, c_i64p, c_f32p, c_i64p, c_f32p, c_i64p, c_f32p, c_i64p, c_f32p,
+                                             c_f32p, c_f32p, C.POINTER(_VP)]),
+    ("dsp_batch_trace_views", C.c_int, [_VP, C.c_int32, c_i64p, c_i64p, c_i64p, c_f32p, C.POINTER(C.c_uint32), c_f32p]),
     ("dsp_batch_destroy", None, [_VP]),
     ("dsp_pack_results", None, [C.c_int32, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p]),
     ("dsp_gather_results", C.c_int, [C.POINTER(_VP), C.c_int32, C.POINTER(c_f32p), c_i32p, c_f32p]),

@@ -189,7 +189,18 @@ struct ObjConst {           // static layout of one object inside the batch arra
     int samp_off;           // segment of the in-sphere sample list (capacity roundup64(n_rays * D))
     int jsdf_off;           // jacobian-point segment, surface term (capacity roundup64(n_pts))
     int jren_off;           // jacobian-point segment, render term (capacity = sample capacity)
+    int view_member;        // 1: one view of a multi-view group (GroupEnt): with < 10 in-sphere samples (loss.py:73-74) the view contributes no render
+                            // rows in that iteration -- the OBJECT's status is decided over the whole group (k_group_reduce); 0: an object of its own
+};
+
+// Multi-view batches (dsp_batch_create_multiview): one entry per batch member.  A group = the views of one object, consecutive members; its
+// first member (view 0, the reference camera) is the leader and carries the object's pose and code; member v samples at T_oc_v = T_oc * t_ref.
+struct GroupEnt {
+    int leader;             // member index of the group's first view
+    int n_members;          // views of the group (read at the leader)
+    int object;             // index of the object = row of the packed results
     int pad;
+    float t_ref[16];        // view camera -> reference camera, rigid (identity for the leader)
 };
 
 struct ObjState {           // per-object optimiser state, lives on the device for the whole run
@@ -324,12 +335,18 @@ void launch_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, con
                  const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s);
 void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow, int term, float* rows,
                   int cap, hipStream_t s);   // jrow (optional): render row i takes its gradient from jgrad row jrow[i]
+// grp / gmk (both or neither; nullptr = every member is an object of its own): multi-view groups -- the members' Gram sums are pooled at the
+// leader (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
-                  hipStream_t s);    // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr);    // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+// the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
+// -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
+void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
 void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
-void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s);
+void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,
+                     const GroupEnt* grp = nullptr);   // grp: one row per OBJECT, written by the group's leader
 
 hipError_t launch_debug_lie(int kind, const float* x_dev, float* out_dev, int n_depth, hipStream_t s);   // testing: exp_sim3 / exp_se3 / rotation prior as k_solve evaluates them
 

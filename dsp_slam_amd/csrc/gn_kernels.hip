@@ -247,7 +247,7 @@ __device__ __forceinline__ void scan_rays_block(const ObjConst& c, ObjState* st,
         ObjState& s = st[b];
         if (which == 0) {
             s.V = total;
-            if (s.status == DSP_STATUS_GOOD && total < 10) s.status = DSP_STATUS_FEW;   // loss.py:73-74
+            if (s.status == DSP_STATUS_GOOD && total < 10 && !c.view_member) s.status = DSP_STATUS_FEW;   // loss.py:73-74 (a view of a group: k_render_scan, k_group_reduce)
         } else if (which == 1) {
             s.K = total;
         } else {
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void k_build_tiles(const ObjConst* oc, ObjStat
                 int status = s.status;
                 // wave-per-ray bookkeeping (k_front_wave) counts V with a running counter and leaves the "< 10 in-sphere samples" rule
                 // (loss.py:73-74; k_scan_rays applies it in the other forms) to the first tile list built from that count
-                if ((apply_few & 1) && !jac && status == DSP_STATUS_GOOD && s.V < 10) { status = DSP_STATUS_FEW; st[b].status = DSP_STATUS_FEW; }
+                if ((apply_few & 1) && !jac && status == DSP_STATUS_GOOD && s.V < 10 && !c.view_member) { status = DSP_STATUS_FEW; st[b].status = DSP_STATUS_FEW; }
                 const bool good = status == DSP_STATUS_GOOD;
                 if (!jac) {
                     n = good ? (mode == 0 ? s.V : s.P) : 0;
@@ -632,7 +632,15 @@ __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjStat
     if (r >= c.n_rays) return;
     const ObjState& s = st[b];
     const int gr = c.ray_off + r;
+    // (a view of a multi-view group with < 10 in-sphere samples: compute_render_loss returns None for it, loss.py:73-74 -- no render rows from
+    // this view in this iteration; its surface points still count)
     if (s.status != DSP_STATUS_GOOD) { if (lane == 0) { kcnt[gr] = 0; mcnt[gr] = 0; } return; }
+    if (c.view_member && s.V < 10) {      // (its few samples keep no row: the row writers find kept samples by de_ds != 0)
+        const unsigned long long vm = raymask[gr];
+        if ((vm >> lane) & 1ull) sdeds[c.samp_off + rayoff[gr] + __popcll(vm & ((1ull << lane) - 1ull))] = 0.f;
+        if (lane == 0) { kcnt[gr] = 0; mcnt[gr] = 0; }
+        return;
+    }
     const unsigned long long mask = raymask[gr];
     const int base = c.samp_off + rayoff[gr];
     const bool in = lane < n_depth && ((mask >> lane) & 1ull);
@@ -1211,6 +1219,114 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const ObjState* st, const f
     gsum[((size_t)b * 2 + term) * (72 * 72) + e] = a;
 }
 
+// Multi-view groups (GroupEnt): the rows of all views of an object are ONE row set (the reference's H = J^T J / M over everything it is
+// given, optimizer.py:159-168), so the members' fp64 Gram sums are added into the leader's -- in member order: the same bits in every run,
+// no float atomics -- and the solve divides by the group's M and K (gmk[2 leader], gmk[2 leader + 1]).  The object's status is decided here:
+// FEW when no view reached 10 in-sphere samples (every compute_render_loss returned None, loss.py:73-74), a member's failure (a singular
+// pose) otherwise; M == 0, K == 0 and a NaN loss are k_solve's tests, on the pooled numbers.  With a trace, the non-leader members' rows
+// get their own state, V, m, K, checksums and depths (the leader's row is k_solve's).
+__global__ __launch_bounds__(256) void k_group_reduce(const GroupEnt* grp, const ObjConst* oc, ObjState* st, double* gsum, int* gmk, int iter,
+                                                      float* trace, int n_obj) {
+    const int b = blockIdx.y, term = blockIdx.z, tid = threadIdx.x;
+    const GroupEnt g = grp[b];
+    if (g.leader != b) return;
+    // (also a group outside a partial re-run: all its members are DSP_STATUS_SKIP.)  The leader's status word is WRITTEN below by one thread of
+    // this launch, and only ever from GOOD to a failure: a workgroup that starts late and reads the failure skips its share of a sum that
+    // nothing reads any more -- k_solve returns for a leader that is not GOOD, the status is final for the run, and every later iteration's
+    // k_gram_reduce / k_group_reduce skip the group.  A workgroup that reads GOOD adds exactly what it would have added anyway.
+    const int lst = st[b].status;
+    if (lst != DSP_STATUS_GOOD) return;
+    const int e = blockIdx.x * 256 + tid;
+    if (e < 72 * 72) {
+        double* dst = gsum + ((size_t)b * 2 + term) * (72 * 72) + e;
+        double a = *dst;
+        for (int v = 1; v < g.n_members; ++v)
+            if (st[b + v].status == DSP_STATUS_GOOD) a += gsum[((size_t)(b + v) * 2 + term) * (72 * 72) + e];
+        *dst = a;
+    }
+    if (blockIdx.x != 0 || term != 0) return;
+    if (tid == 0) {
+        int M = 0, K = 0, bad = DSP_STATUS_GOOD;
+        bool any = false;
+        for (int v = 0; v < g.n_members; ++v) {
+            const ObjState& s = st[b + v];
+            if (s.status != DSP_STATUS_GOOD) { if (bad == DSP_STATUS_GOOD) bad = s.status; continue; }
+            M += oc[b + v].n_pts;
+            K += s.K;
+            any = any || s.V >= 10;
+        }
+        gmk[2 * b] = M;
+        gmk[2 * b + 1] = K;
+        if (!any) st[b].status = DSP_STATUS_FEW;
+        else if (bad != DSP_STATUS_GOOD) st[b].status = bad;
+    }
+    if (trace)
+        for (int v = 1; v < g.n_members; ++v) {
+            const ObjState& s = st[b + v];
+            float* tr = trace + ((size_t)iter * n_obj + b + v) * TRACE_STRIDE + NSOLVE * NSOLVE + 2 * NSOLVE;
+            if (tid < 16) tr[tid] = s.t_oc[tid];
+            if (tid < 64) { tr[16 + tid] = s.code[tid]; tr[5280 - (NSOLVE * NSOLVE + 2 * NSOLVE) + tid] = s.depths[tid]; }
+            if (tid == 0) {
+                tr[80] = (float)s.V; tr[81] = (float)s.m; tr[82] = (float)s.K;
+                tr[83] = (float)(s.vsum & 0xffffu); tr[84] = (float)(s.vsum >> 16);
+                tr[85] = (float)(s.ksum & 0xffffu); tr[86] = (float)(s.ksum >> 16);
+            }
+        }
+}
+
+// Behind k_solve (and once behind k_init_state): every non-leader member takes the object's new state.  t_oc_v = T_oc * t_ref_v, the fp64
+// product of the two fp32 matrices rounded once; the per-iteration derived state as k_solve derives the leader's (derive_iter_core; depths:
+// the forensic override); code, margin and the code-bias row are the leader's.  The update is a LEFT perturbation in the object frame,
+// exp(dx) T_oc T_ref_v = exp(dx) T_oc_v (optimizer.py:187-188), so no view needs a jacobian of its own.  A failed leader stops its members.
+__global__ __launch_bounds__(64) void k_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const GroupEnt g = grp[b];
+    if (g.leader == b) return;
+    const ObjState& l = st[g.leader];
+    ObjState& s = st[b];
+    const int lst = l.status;
+    if (lst == DSP_STATUS_SKIP) return;
+    if (lst != DSP_STATUS_GOOD) { if (lane == 0) s.status = lst; return; }
+    float nt[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc += (double)l.t_oc[4 * r + k] * (double)g.t_ref[4 * k + cc];
+            nt[4 * r + cc] = (float)acc;
+        }
+    const IterDerived r = derive_iter_core(nt, n_depth);
+    s.code[lane] = l.code[lane];
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s.t_oc[i] = nt[i];
+        s.lp_delta = l.lp_delta;
+        s.vsum = 0; s.ksum = 0;
+        s.V = 0; s.P = 0;
+        s.status = r.ok ? DSP_STATUS_GOOD : DSP_STATUS_NAN;
+    }
+    if (r.ok) {
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s.t_co[i] = r.t_co[i];
+            s.scale = r.scale;
+        }
+        const float* dn = depths ? depths + MAX_DEPTH_SAMPLES * b : nullptr;
+        if (lane < n_depth) s.depths[lane] = dn ? dn[lane] : linspace_at(r, lane, n_depth);
+        if (lane == 0) {
+            s.dmin = dn ? dn[0] : r.dmin;
+            s.dmax = dn ? dn[n_depth - 1] : r.dmax;
+        }
+    }
+    if (cbias) {
+        const float4* src = reinterpret_cast<const float4*>(cbias + (size_t)g.leader * 2 * WIDTH);
+        float4* dst = reinterpret_cast<float4*>(cbias + (size_t)b * 2 * WIDTH);
+        for (int i = lane; i < 2 * WIDTH / 4; i += 64) dst[i] = src[i];
+    }
+}
+
 constexpr int SOLVE_THREADS = 1024;   // 16 waves: assembly, trace and the code bias use all of them; the elimination nine
 constexpr int NS1 = NSOLVE + 1;       // rows of the augmented system: the unknowns + the right-hand side as row n
 
@@ -1227,16 +1343,24 @@ __device__ __forceinline__ double fast_recip(double d) {
 // pivots.  (Earlier forms -- one barrier per pivot, packed LDL^T, Gauss-Jordan on 16 waves -- and their measurements: profiles/r06_removed_experiments.md.)
 template <bool V> struct BoolC { static constexpr bool value = V; };
 
+// GROUPS (multi-view batches): only a group's leader solves, with the group's pooled Gram sums (k_group_reduce) and its M and K from gmk;
+// GROUPS = false is the code of every other batch, untouched by the group form (a template argument, not a run-time test: k_solve sits on
+// the detection's latency path).
+template <bool GROUPS>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int iter,
                                                          const float* codew, const float* cb0, const float* cblat, float* cbias,
-                                               float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj) {
+                                               float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj,
+                                               const GroupEnt* grp, const int* gmk) {
     __shared__ double A[NS1][NS1 + 1];          // [H | b] in rows 0..n-1 (b = column n); b is also kept as ROW n (rows 64 .. 71 are one register of the elimination)
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (GROUPS) { if (grp[b].leader != b) return; }
     const ObjConst c = oc[b];
     ObjState& s = st[b];
     // Everything this launch reads from global memory goes out HERE, before the first of it is waited for -- the status word included
     // (k_solve is a chain of latencies: status -> Gram loads -> state for the prior -> ... was three round trips of ~1 us each).
-    const int status = s.status, K = s.K;
+    const int status = s.status;
+    int K = s.K;
+    if constexpr (GROUPS) K = gmk[2 * b + 1];
     float pr_tco[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) pr_tco[i] = s.t_co[i];
@@ -1250,7 +1374,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     const double* G0p = gsum + ((size_t)b * 2 + 0) * (72 * 72);
     const double* G1p = gsum + ((size_t)b * 2 + 1) * (72 * 72);
     auto gram = [=](int term, int idx) -> double { return (term ? G1p : G0p)[idx]; };
-    const int M = c.n_pts;
+    int M = c.n_pts;
+    if constexpr (GROUPS) M = gmk[2 * b];
     const int pd = prm.pose_only ? 6 : 7;
     const int n = prm.pose_only ? 6 : NSOLVE;
     // thread (tr, tc) fills column tc of rows tr, tr+12, ... of the joint system: its Gram loads
@@ -1581,17 +1706,24 @@ __global__ __launch_bounds__(256) void k_count_alive(const ObjConst* oc, ObjStat
 // final result: T_co = inv(T_oc) (optimizer.py:200; 81-84 for pose-only, which also divides the scale out), as ONE DSP_RESULT_WIDTH row per
 // object (t_cam_obj 16 | code 64 | loss | status): what dsp_batch_results unpacks and what the multi-GPU gather sends, device-resident.
 // guard_out (optional): the always-on prepass guard's per-object words {lp_delta, trips, max error bits}, packed for the run's ONE read-back.
-__global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int pose_only, float* out_packed, unsigned* guard_out) {
+__global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int pose_only, float* out_packed, unsigned* guard_out, const GroupEnt* grp) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_obj) return;
     const ObjState& s = st[b];
     if (s.status == DSP_STATUS_SKIP) return;      // partial re-run: the row of the earlier run stands
+    if (guard_out) {
+        guard_out[3 * b + 0] = __float_as_uint(s.lp_delta);
+        guard_out[3 * b + 1] = s.guard_trips;
+        guard_out[3 * b + 2] = s.guard_err;
+    }
+    if (grp && grp[b].leader != b) return;        // multi-view groups: one row per OBJECT, from the group's leader
+    const int row_i = grp ? grp[b].object : b;
     double toc[16], tco[16];
     for (int i = 0; i < 16; ++i) toc[i] = (double)s.t_oc[i];
     if (!inv4(toc, tco)) for (int i = 0; i < 16; ++i) tco[i] = nan("");
     // pose-only with no point left (J^T J / 0, optimizer.py:69-72): the reference's pose is NaN from then on, and so is this one
     if (pose_only && s.status == DSP_STATUS_NAN) for (int i = 0; i < 16; ++i) tco[i] = nan("");
-    float* row = out_packed + (size_t)DSP_RESULT_WIDTH_DEV * b;
+    float* row = out_packed + (size_t)DSP_RESULT_WIDTH_DEV * row_i;
     for (int i = 0; i < 16; ++i) {
         float v = (float)tco[i];
         if (pose_only && (i % 4) < 3 && i < 12) v = v / scale_in[b];
@@ -1600,11 +1732,6 @@ __global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int p
     for (int i = 0; i < CODE_LEN; ++i) row[16 + i] = s.code[i];
     row[80] = s.loss;
     row[81] = (float)s.status;
-    if (guard_out) {
-        guard_out[3 * b + 0] = __float_as_uint(s.lp_delta);
-        guard_out[3 * b + 1] = s.guard_trips;
-        guard_out[3 * b + 2] = s.guard_err;
-    }
 }
 
 // per-object code contribution to layer 0 and to the latent_in layer (one workgroup per object):
@@ -1720,16 +1847,28 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
     hipLaunchKernelGGL(k_jrows, dim3((cap + 255) / 256), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, term, rows);
 }
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
-                  float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s) {
+                  float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
+                  const GroupEnt* grp, int* gmk) {
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
-    hipLaunchKernelGGL(k_solve, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B);
+    if (!grp) {
+        hipLaunchKernelGGL(k_solve<false>, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
+                           (const GroupEnt*)nullptr, (const int*)nullptr);
+        return;
+    }
+    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B);
+    hipLaunchKernelGGL(k_solve<true>, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
+                       (const int*)gmk);
+    launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
+}
+void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_group_broadcast, dim3(B), dim3(64), 0, s, grp, st, cbias, depths, n_depth);
 }
 void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_inlier_filter, GRID2(maxM, B), dim3(256), 0, s, oc, st, jgrad, alive);
     hipLaunchKernelGGL(k_count_alive, dim3(B), dim3(256), 0, s, oc, st, alive);
 }
-void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out, hipStream_t s) {
-    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, st, scale, B, pose_only, packed, guard_out);
+void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out, hipStream_t s, const GroupEnt* grp) {
+    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, st, scale, B, pose_only, packed, guard_out, grp);
 }
 
 // Testing (dsp_debug_lie): the Lie-group maps and the rotation prior exactly as k_solve evaluates them -- ONE thread, the same device

@@ -253,6 +253,80 @@ class Batch(object):
             pass
 
 
+def _flatten_views(views_per_object):
+    """[[dict(t_ref_cam, pts, rays, depth), ...] per object] -> (view_off int64 (n + 1), t_ref (n_views, 4, 4), pts / rays / depth lists per view)."""
+    off = np.zeros(len(views_per_object) + 1, np.int64)
+    off[1:] = np.cumsum([len(v) for v in views_per_object])
+    flat = [v for views in views_per_object for v in views]
+    t_ref = L.f32(np.stack([np.asarray(v["t_ref_cam"], np.float32).reshape(4, 4) for v in flat])) if flat else np.zeros((1, 4, 4), np.float32)
+    return (off, t_ref, [L.f32(v["pts"]).reshape(-1, 3) for v in flat], [L.f32(v["rays"]).reshape(-1, 3) for v in flat],
+            [L.f32(v["depth"]).reshape(-1) for v in flat])
+
+
+class MultiviewBatch(Batch):
+    """Device-resident multi-view batch (dsp_batch_create_multiview): every object has ONE pose and ONE code and a list of views
+    dict(t_ref_cam (4, 4) rigid view camera -> reference camera, pts, rays, depth) -- the first view is the reference camera (identity).
+    run / results / stats / the setters / trace work as on a Batch, per object; set_start_state takes t_obj_cam and codes per object and
+    depths per view; trace_views gives the per-view counts."""
+
+    def __init__(self, engine, prm, t_cam_obj, views, codes=None, trace=False):
+        self.engine = engine
+        self.n = len(views)
+        self.pose_only = False
+        vo, t_ref, pts, rays, depth = _flatten_views(views)
+        self.n_views = int(vo[-1])
+        self.view_off = vo
+        self._keep = (
+            vo, t_ref, _ragged(pts, 3), _ragged(rays, 3), _ragged(depth, 0),
+            L.f32(np.stack([np.asarray(t, np.float32).reshape(4, 4) for t in t_cam_obj])),
+            None if codes is None else L.f32(np.stack([L.code64(c) for c in codes])),
+        )
+        _, _, (po, p), (ro, r), (do, d), t, c = self._keep
+        self._h = C.c_void_p()
+        lib = L.load()
+        L.check(lib.dsp_batch_create_multiview(engine._h, C.byref(prm), self.n, L.ptr(vo, L.c_i64p), L.ptr(t_ref), L.ptr(po, L.c_i64p), L.ptr(p),
+                                               L.ptr(ro, L.c_i64p), L.ptr(r), L.ptr(do, L.c_i64p), L.ptr(d), L.ptr(t), L.ptr(c), C.byref(self._h)),
+                engine._h, "dsp_batch_create_multiview")
+        self.iters = prm.num_iterations
+        engine._batches.add(self)
+        if trace:
+            L.check(lib.dsp_batch_enable_trace(self._h, 1), engine._h, "dsp_batch_enable_trace")
+
+    def set_start_state(self, t_obj_cam=None, codes=None, depths=None):
+        """t_obj_cam / codes: one per object; depths: one row per VIEW (all objects' views in order)."""
+        t = None if t_obj_cam is None else L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_obj_cam]))
+        c = None if codes is None else L.f32(np.stack([L.code64(x) for x in codes]))
+        d = None
+        if depths is not None:
+            d = np.zeros((self.n_views, 64), np.float32)
+            for i, row in enumerate(depths):
+                row = np.asarray(row, np.float32).reshape(-1)
+                d[i, :row.shape[0]] = row
+        L.check(L.load().dsp_batch_debug_start_state(self._h, L.ptr(t), L.ptr(c), L.ptr(d)), self.engine._h, "dsp_batch_debug_start_state")
+
+    def set_depth_schedule(self, depths=None):
+        """depths[e][v] = the depth samples VIEW v uses in iteration e."""
+        if depths is None:
+            return Batch.set_depth_schedule(self, None)
+        n_it = len(depths)
+        d = np.zeros((n_it, self.n_views, 64), np.float32)
+        for e in range(n_it):
+            for i in range(self.n_views):
+                row = np.asarray(depths[e][i], np.float32).reshape(-1)
+                d[e, i, :row.shape[0]] = row
+        L.check(L.load().dsp_batch_debug_depth_schedule(self._h, L.ptr(d), n_it), self.engine._h, "dsp_batch_debug_depth_schedule")
+
+    def trace_views(self, iteration):
+        """Per view of one iteration of the last run: V, m, K, t_obj_cam (T_oc_v), set_sums, depths."""
+        n = self.n_views
+        out = dict(V=np.zeros(n, np.int64), m=np.zeros(n, np.int64), K=np.zeros(n, np.int64), t_obj_cam=np.zeros((n, 4, 4), np.float32),
+                   set_sums=np.zeros((n, 2), np.uint32), depths=np.zeros((n, 64), np.float32))
+        L.check(L.load().dsp_batch_trace_views(self._h, int(iteration), L.ptr(out["V"], L.c_i64p), L.ptr(out["m"], L.c_i64p), L.ptr(out["K"], L.c_i64p),
+                                               L.ptr(out["t_obj_cam"]), L.ptr(out["set_sums"], C.POINTER(C.c_uint32)), L.ptr(out["depths"])),
+                self.engine._h, "dsp_batch_trace_views")
+        return out
+
+
 def gather_results_c(engines, packed):
     """dsp_gather_results: one RCCL gather, inside ONE process, of the (n_i, 82) result blocks of several engines (one per GPU)
     to the first engine's GPU; returns them concatenated in engine order.  (Across processes use dsp_slam_amd.distributed.)"""
@@ -539,6 +613,28 @@ class Engine(object):
             return b.results()
         finally:
             b.close()
+
+    def multiview_batch(self, prm, t_cam_obj, views, codes=None, trace=False):
+        """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
+        return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
+
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None):
+        """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object."""
+        n = len(views)
+        if n == 0:
+            return (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+        vo, t_ref, pts, rays, depth = _flatten_views(views)
+        (po, p), (ro, r), (do, d) = _ragged(pts, 3), _ragged(rays, 3), _ragged(depth, 0)
+        t = L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_cam_obj]))
+        c = None if codes is None else L.f32(np.stack([L.code64(x) for x in codes]))
+        t_out = np.zeros((n, 4, 4), np.float32)
+        code = np.zeros((n, L.CODE_LEN), np.float32)
+        loss = np.zeros(n, np.float32)
+        status = np.zeros(n, np.int32)
+        L.check(L.load().dsp_reconstruct_multiview(self._h, C.byref(prm), n, L.ptr(vo, L.c_i64p), L.ptr(t_ref), L.ptr(po, L.c_i64p), L.ptr(p),
+                                                   L.ptr(ro, L.c_i64p), L.ptr(r), L.ptr(do, L.c_i64p), L.ptr(d), L.ptr(t), L.ptr(c), L.ptr(t_out),
+                                                   L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
+        return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
     def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes):
         n = len(pts)

@@ -99,6 +99,20 @@ class Optimizer(object):
             print("Reconstruction takes %f seconds" % (get_time() - start))
         return rst
 
+    def reconstruct_object_multiview(self, t_cam_obj, views, code=None):
+        """Joint shape + pose optimisation of one object from SEVERAL observations (an addition: the reference's reconstruct_object,
+        optimizer.py:88-203, takes one, although its map keeps one per key frame).  t_cam_obj: (4, 4) Sim(3) object-to-camera start in the
+        frame of the REFERENCE camera = the camera of views[0]; views: [dict(t_ref_cam, pts, rays, depth), ...] -- t_ref_cam (4, 4) rigid,
+        that view's camera -> the reference camera (identity for views[0]); pts / rays / depth as reconstruct_object takes them, in that
+        view's camera frame.  All views share one pose and one code; their rows are pooled into one Gauss-Newton system per iteration.
+        Same result dict as reconstruct_object; one view gives reconstruct_object's result, bit for bit."""
+        vs = [dict(t_ref_cam=_f32(v["t_ref_cam"]), pts=_f32(v["pts"]), rays=_f32(v["rays"]), depth=_f32(v["depth"]).reshape(-1)) for v in views]
+        codes_in = None if code is None else [_f32(code)[:self.code_len]]
+        t, z, loss, status = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in)
+        if status[0] == _L.OBJ_GOOD:
+            return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])))
+        return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[0]))
+
     @staticmethod
     def get_shape_code(result):
         """Shape code of a reconstruction result (the C++ side keeps it in MapObject::GetShapeCode,

@@ -268,3 +268,65 @@ def make_object(seed, n_surface=2000, n_background=500, code_len=64,
 
 def make_batch(n_objects, first_seed=0, **kw):
     return [make_object(first_seed + i, **kw) for i in range(n_objects)]
+
+
+def make_object_multiview(seed, n_views=3, n_surface=600, n_background=150, code_len=64, t_noise=0.25, yaw_noise_deg=5.0,
+                          yaw_spread_deg=120.0, half=None):
+    """One synthetic rounded-box object seen from n_views cameras (an addition beside make_object, which it leaves alone).
+
+    Camera 0 is the reference camera.  Camera v stands at the same distance from the object, turned about the object's vertical axis by
+    v * yaw_spread_deg / max(n_views - 1, 1) -- so each camera sees another side -- and gets its own camera-facing surface points, pixel
+    rays, depths and background rays, all in ITS frame.  Returns a dict: t_cam_obj_gt / t_cam_obj_init (4, 4) Sim(3) object -> reference
+    camera, code_gt, scale, and views = [dict(t_ref_cam (4, 4) rigid view camera -> reference camera, pts, rays, depth), ...] (float32;
+    views[0]["t_ref_cam"] is the identity).
+    """
+    rng = np.random.default_rng(7000 + seed)
+    code_gt = np.zeros(code_len)
+    code_gt[:3] = rng.normal(scale=0.3, size=3)
+    scale = rng.uniform(1.8, 2.2)
+    theta = rng.uniform(-np.pi, np.pi)
+    t = np.array([rng.uniform(-2.0, 2.0), 1.2, rng.uniform(8.0, 16.0)])
+    flip = np.diag([1.0, -1.0, -1.0])
+
+    def pose(yaw):
+        m = np.eye(4)
+        m[:3, :3] = scale * (rot_y(yaw) @ flip)
+        m[:3, 3] = t
+        return m
+
+    t_co_ref = pose(theta)
+    views = []
+    for v in range(n_views):
+        yaw = theta + np.deg2rad(yaw_spread_deg) * v / max(n_views - 1, 1)
+        t_co = pose(yaw)
+        r_co = t_co[:3, :3] / scale
+        cam_o = r_co.T @ (-t) / scale
+        pts_o = np.zeros((0, 3))
+        while pts_o.shape[0] < n_surface:
+            cand = surface_points(code_gt[:3], 4 * max(n_surface, 1), rng, half)
+            nrm = _sdf_normal(cand, code_gt[:3], half=half)
+            vis = np.einsum("ij,ij->i", nrm, cam_o[None, :] - cand) > 0.05
+            pts_o = np.concatenate([pts_o, cand[vis]], axis=0)
+        pts_c = pts_o[:n_surface] @ t_co[:3, :3].T + t
+        fg_rays = pts_c / pts_c[:, 2:3]
+        lo, hi = fg_rays[:, :2].min(0) - 0.05, fg_rays[:, :2].max(0) + 0.05
+        bg = np.zeros((0, 3))
+        while bg.shape[0] < n_background:
+            uv = rng.uniform(lo, hi, size=(4 * n_background, 2))
+            d_c = np.concatenate([uv, np.ones((uv.shape[0], 1))], axis=-1)
+            d_o = d_c @ r_co
+            d_o /= np.linalg.norm(d_o, axis=-1, keepdims=True)
+            hit = _ray_hits_shape(np.repeat(cam_o[None, :], uv.shape[0], 0), d_o, code_gt[:3], half=half)
+            bg = np.concatenate([bg, d_c[~hit]], axis=0)
+        t_ref_cam = np.eye(4) if v == 0 else t_co_ref @ np.linalg.inv(t_co)      # same scale on both sides: rigid
+        views.append(dict(t_ref_cam=t_ref_cam.astype(np.float32), pts=np.ascontiguousarray(pts_c, dtype=np.float32),
+                          rays=np.ascontiguousarray(np.concatenate([fg_rays, bg[:n_background]], axis=0), dtype=np.float32),
+                          depth=np.ascontiguousarray(pts_c[:, 2], dtype=np.float32)))
+    dyaw = np.deg2rad(yaw_noise_deg) * rng.uniform(-1.0, 1.0)
+    dt = rng.normal(size=3)
+    dt *= t_noise / np.linalg.norm(dt)
+    t_init = np.eye(4)
+    t_init[:3, :3] = scale * (rot_y(theta + dyaw) @ flip)
+    t_init[:3, 3] = t + dt
+    return dict(t_cam_obj_gt=t_co_ref.astype(np.float32), t_cam_obj_init=t_init.astype(np.float32), code_gt=code_gt.astype(np.float32),
+                scale=np.float32(scale), views=views)

@@ -186,6 +186,26 @@ int dsp_reconstruct_batch(dsp_handle* h, const dsp_gn_params* prm, int32_t n_obj
                           const float* depth, const float* t_cam_obj_in, const float* codes_in,
                           float* t_cam_obj_out, float* codes_out, float* loss_out, int32_t* status_out);
 
+/* MULTI-VIEW reconstruction (an addition; the reference optimises an object from ONE observation, optimizer.py:88-203, although its map holds
+ * one per key frame, src/Optimizer_util.cc:196-217): object i has one Sim(3) pose and one code, observed by the views
+ * view_off[i] .. view_off[i+1]-1 (at least one).  View v has t_ref_view[v] (4x4 rigid: view-v camera -> the object's reference camera; the
+ * object's first view IS the reference camera: identity) and its own pts / rays / depth in ITS camera frame -- pts_off, ray_off, depth_off
+ * have n_views + 1 entries, laid out as dsp_reconstruct_batch lays them out per object; any of a view's counts may be 0.  t_cam_obj_in /
+ * codes_in and the outputs are per OBJECT (t_cam_obj in the reference camera's frame).  Per iteration, with T_oc_v = T_oc * t_ref_view[v]:
+ *   - per view exactly the reference's two terms at T_oc_v: compute_sdf_loss (loss.py:22-43) and compute_render_loss (loss.py:46-152) with the
+ *     depth samples and the background depth derived from T_oc_v as optimizer.py:120-126 derives them from T_oc; a view whose render term is
+ *     None (< 10 in-sphere samples, loss.py:73-74) contributes no render rows in that iteration (it may in a later one);
+ *   - the rows of all views are ONE row set: H = k2 sum J^T J / sum M_v + k1 sum J^T J / sum K_v, b and the loss likewise (optimizer.py:134-168);
+ *     code prior, rotation prior (from T_oc), damping, solve and the update T_oc <- exp_sim3(dx) T_oc as optimizer.py:170-192 -- the update is
+ *     a left perturbation in the object frame, so it moves every T_oc_v alike.
+ * Status: DSP_OBJ_FEW_SAMPLES when no view reached 10 in-sphere samples; DSP_OBJ_NAN when sum M_v == 0, sum K_v == 0 or a loss is NaN.
+ * With one view per object the result is dsp_reconstruct_batch's, bit for bit.  DSP_E_ARG: view_off not increasing from 0 (an object
+ * without views), a t_ref_view that is not rigid (R^T R - I or the bottom row off by more than 1e-4), a first view that is not the identity. */
+int dsp_reconstruct_multiview(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* view_off, const float* t_ref_view,
+                              const int64_t* pts_off, const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,
+                              const float* depth, const float* t_cam_obj_in, const float* codes_in, float* t_cam_obj_out, float* codes_out,
+                              float* loss_out, int32_t* status_out);
+
 /* Optimizer.estimate_pose_cam_obj for a ragged batch -- reconstruct/optimizer.py:45-86.
  * t_co_se3_in[i] (4x4 SE(3)), scale[i], pts as above, codes[i] (64).  Output t_co_se3_out[i] (4x4 SE(3)).
  * The inputs are not modified (the reference scales the caller's matrix in place, :53-54).
@@ -249,6 +269,13 @@ int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects,
  * dsp_estimate_pose_batch's t_co_se3_out, bit for bit; its codes are the input codes and its loss is 0. */
 int dsp_batch_create_pose(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off, const float* pts,
                           const float* t_co_se3_in, const float* scale, const float* codes, dsp_batch** out);
+/* The batch of dsp_reconstruct_multiview (same inputs), device-resident.  dsp_batch_run / _results (per object) / _stats / the setters /
+ * _enable_trace / _trace / _destroy and both gathers work on it; dsp_batch_set_compute refuses the low-precision mode (DSP_E_ARG).
+ * dsp_batch_debug_start_state takes t_obj_cam and codes per OBJECT and depths per VIEW (n_views x 64); dsp_batch_debug_depth_schedule and
+ * dsp_batch_debug_samples count VIEWS where they say objects.  A prepass-guard trip on any view re-runs the whole object. */
+int dsp_batch_create_multiview(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* view_off, const float* t_ref_view,
+                               const int64_t* pts_off, const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,
+                               const float* depth, const float* t_cam_obj_in, const float* codes_in, dsp_batch** out);
 int dsp_batch_run(dsp_batch* b);        /* resets the state to the uploaded initial estimate, runs, synchronises */
 int dsp_batch_results(dsp_batch* b, float* t_cam_obj_out, float* codes_out, float* loss_out, int32_t* status_out);
 int dsp_batch_stats(dsp_batch* b, dsp_stats* out);
@@ -368,6 +395,13 @@ int dsp_batch_enable_trace(dsp_batch* b, int on);
  * no point only K (= 0) is written. */
 int dsp_batch_trace(dsp_batch* b, int32_t iteration, float* H, float* bvec, float* dx, int64_t* V, int64_t* m,
                     int64_t* K, float* t_obj_cam, float* code, uint32_t* set_sums, float* depths /* 64 per object */);
+/* A multi-view batch (dsp_batch_create_multiview): dsp_batch_trace returns, per OBJECT, the pooled H, b, dx, the object's state, the
+ * reference view's depths, and V, m, K summed over its views (set_sums is zero there: a checksum belongs to one view's sample set, whose
+ * ray indices are the view's own); this call returns them per VIEW:
+ * V, m, K (n_views), t_obj_cam (n_views x 16: T_oc_v), set_sums (n_views x 2), depths (n_views x 64).  A view with V < 10 has K = 0.  Any
+ * pointer may be NULL; DSP_E_ARG for any other kind of batch. */
+int dsp_batch_trace_views(dsp_batch* b, int32_t iteration, int64_t* V, int64_t* m, int64_t* K, float* t_obj_cam, uint32_t* set_sums,
+                          float* depths /* 64 per view */);
 void dsp_batch_destroy(dsp_batch* b);
 
 /* ---- multi-GPU: objects are independent, so GPUs take disjoint blocks of the object list (one handle per GPU, one host

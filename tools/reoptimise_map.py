@@ -9,6 +9,10 @@ LocalMapping hands to Optimizer.reconstruct_object, src/LocalMapping_util.cc:179
     <map_dir>/observations/<id>.npz :  pts (M,3) surface points, rays (R,3) ray directions (foreground rows first), depth (n_fg,)
                                        observed depths, all in the frame of the observing camera; t_world_cam (4,4) that camera's pose
 
+An object seen from several key frames may have further files observations/<id>.<k>.npz (k = 1, 2, ...; same arrays, each with its own
+t_world_cam): where any exist, the object is optimised over ALL its views -- one pose and one code, the first file's camera as the reference
+camera (dsp_reconstruct_multiview).  A map without such files runs exactly as before.
+
 Every object with an observation file is optimised jointly (shape code + Sim(3) pose) as ONE ragged batch per GPU, warm-started from the
 saved code and pose: objects are block-sharded over the GPUs by estimated cost (dsp_slam_amd.distributed.shard_objects), each shard runs
 as one dsp_batch on its own handle from its own host thread, and the result rows are gathered once.  Objects whose optimisation fails
@@ -29,6 +33,11 @@ sys.path.insert(0, os.path.join(ROOT, "dsp_slam_amd"))
 sys.path.insert(0, ROOT)
 
 
+def _read_observation(z):
+    return dict(pts=np.ascontiguousarray(z["pts"], np.float32), rays=np.ascontiguousarray(z["rays"], np.float32),
+                depth=np.ascontiguousarray(z["depth"], np.float32).reshape(-1), t_world_cam=np.asarray(z["t_world_cam"], np.float64))
+
+
 def load_observations(map_dir, objs):
     """-> list parallel to objs: dict(pts, rays, depth, t_world_cam) or None."""
     out = []
@@ -38,9 +47,24 @@ def load_observations(map_dir, objs):
             out.append(None)
             continue
         z = np.load(p)
-        out.append(dict(pts=np.ascontiguousarray(z["pts"], np.float32), rays=np.ascontiguousarray(z["rays"], np.float32),
-                        depth=np.ascontiguousarray(z["depth"], np.float32).reshape(-1), t_world_cam=np.asarray(z["t_world_cam"], np.float64)))
+        ob = _read_observation(z)
+        more, k = [], 1
+        while os.path.exists(os.path.join(map_dir, "observations", "%d.%d.npz" % (o["id"], k))):      # further views of the same object
+            more.append(_read_observation(np.load(os.path.join(map_dir, "observations", "%d.%d.npz" % (o["id"], k)))))
+            k += 1
+        if more:
+            ob["more_views"] = more
+        out.append(ob)
     return out
+
+
+def object_views(ob):
+    """The views of one observed object as dsp_reconstruct_multiview takes them: the first file's camera is the reference camera."""
+    inv0 = np.linalg.inv(ob["t_world_cam"])
+    views = [dict(t_ref_cam=np.eye(4, dtype=np.float32), pts=ob["pts"], rays=ob["rays"], depth=ob["depth"])]
+    for v in ob.get("more_views", []):
+        views.append(dict(t_ref_cam=(inv0 @ v["t_world_cam"]).astype(np.float32), pts=v["pts"], rays=v["rays"], depth=v["depth"]))
+    return views
 
 
 def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
@@ -54,14 +78,22 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
         t_wc = obs[i]["t_world_cam"]
         t_in.append((np.linalg.inv(t_wc) @ np.asarray(objs[i]["pose"], np.float64)).astype(np.float32))     # object -> camera, the optimiser's frame
         codes_in.append(np.asarray(objs[i]["code"], np.float32)[:code_len])
+    views = {i: object_views(obs[i]) for i in idx}
     if shards is None:
-        shards = D.shard_objects([D.object_cost(obs[i]["pts"].shape[0], obs[i]["rays"].shape[0], prm.num_depth_samples) for i in idx], len(engines))
+        shards = D.shard_objects([sum(D.object_cost(v["pts"].shape[0], v["rays"].shape[0], prm.num_depth_samples) for v in views[i]) for i in idx],
+                                 len(engines))
     parts = [None] * len(shards)
+    multiview = any("more_views" in obs[i] for i in idx)
+    if multiview and compute != 0:
+        raise ValueError("the low-precision compute mode does not take multi-view objects")
 
     def work(r):
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
+        if multiview:      # one-view objects of such a map go through the same call: one view IS reconstruct_batch, bit for bit
+            parts[r] = D.pack_results(*eng.reconstruct_multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b]))
+            return
         res = eng.reconstruct_batch(prm, t_in[a:b], [obs[i]["pts"] for i in sel], [obs[i]["rays"] for i in sel], [obs[i]["depth"] for i in sel],
                                     codes_in[a:b], compute=compute)
         parts[r] = D.pack_results(*res)

@@ -93,6 +93,8 @@ SYMBOLS = [
     ("dsp_batch_set_kernel_timing", C.c_int, [_VP, C.c_int]),
     ("dsp_batch_set_iterations", C.c_int, [_VP, C.c_int32]),
     ("dsp_batch_set_compute", C.c_int, [_VP, C.c_int]),
+    ("dsp_batch_convergence", C.c_int, [_VP, C.c_float, C.c_float, C.c_int32]),
+    ("dsp_batch_iterations_used", C.c_int, [_VP, c_i32p]),
     ("dsp_sdf_jacobian_lp", C.c_int, [_VP, C.c_int, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p]),
     ("dsp_batch_set_debug", C.c_int, [_VP, C.c_int, C.c_int]),
     ("dsp_prepass_calibration", C.c_int, [_VP, C.c_int, c_f32p, c_f32p]),

@@ -179,6 +179,9 @@ constexpr int DSP_STATUS_GOOD = 0;
 constexpr int DSP_STATUS_FEW = 1;    // < 10 in-sphere samples (loss.py:73-74)
 constexpr int DSP_STATUS_NAN = 2;    // NaN loss / singular system (optimizer.py:135-136,149-150)
 constexpr int DSP_STATUS_SKIP = 3;   // internal: not part of this (partial re-)run; never leaves the library (k_init_state run_mask, k_finalize)
+// internal: converged under the batch's convergence rule (dsp_batch_convergence) and FROZEN for the rest of the run: like SKIP it is
+// "not GOOD" to every kernel -- no tiles, rows, guard samples, no write to the state -- but k_finalize writes its row and reports DSP_OBJ_GOOD
+constexpr int DSP_STATUS_DONE = 4;
 constexpr int MAX_DEPTH_SAMPLES = 64;
 constexpr int TRACE_STRIDE = 5344;   // 71*71 H | 71 b | 71 dx | 16 t_oc | 64 code | V m K | vsum lo,hi | ksum lo,hi | pad | 64 depths
 
@@ -217,7 +220,7 @@ struct ObjState {           // per-object optimiser state, lives on the device f
     float lp_delta;
     unsigned guard_trips;   // waves that re-decoded a sample whose prepass value was off by >= lp_delta / 2
     unsigned guard_err;     // largest |sdf_lp - sdf_fp32| over the re-decoded samples (float bits)
-    int pad0;
+    int n_iter;             // Gauss-Newton updates applied so far in this run (k_solve; dsp_batch_iterations_used)
 };
 
 #ifdef __HIPCC__
@@ -269,6 +272,14 @@ struct GnParamsDev {
     int n_depth, pose_only;
     int code_len;       // of the decoder (32 or 64); the state always carries CODE_LEN entries
     LpDeltaTab lp;      // prepass margin table of the dtype in use (all entries equal when the caller fixed delta)
+};
+
+// Convergence rule of a run (dsp_batch_convergence), evaluated by k_solve<., true> in fp64 on the step it has just applied: the object is
+// frozen (DSP_STATUS_DONE) when iter + 1 >= min_iterations, every |lr dx_pose| < pose_tol and every |lr dx_code| < code_tol (strict: a
+// tolerance of 0 stops nothing, +inf switches its half off, a NaN step never passes)
+struct StopRule {
+    double pose_tol, code_tol;
+    int min_iterations;
 };
 
 // kernels_mlp / kernels_gn launchers
@@ -339,14 +350,14 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 // leader (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
-                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr);    // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr);    // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
 // the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
 // -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
 void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
 void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,
-                     const GroupEnt* grp = nullptr);   // grp: one row per OBJECT, written by the group's leader
+                     const GroupEnt* grp = nullptr, unsigned* iters_out = nullptr /*optional B: ObjState::n_iter*/);   // grp: one row per OBJECT, written by the group's leader
 
 hipError_t launch_debug_lie(int kind, const float* x_dev, float* out_dev, int n_depth, hipStream_t s);   // testing: exp_sim3 / exp_se3 / rotation prior as k_solve evaluates them
 

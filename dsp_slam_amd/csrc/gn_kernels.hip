@@ -245,6 +245,7 @@ __device__ __forceinline__ void scan_rays_block(const ObjConst& c, ObjState* st,
     if (tid == NT - 1) {
         const int total = part[2 * NWV - 1];
         ObjState& s = st[b];
+        if (s.status == DSP_STATUS_DONE) return;      // frozen (convergence rule): its state is final
         if (which == 0) {
             s.V = total;
             if (s.status == DSP_STATUS_GOOD && total < 10 && !c.view_member) s.status = DSP_STATUS_FEW;   // loss.py:73-74 (a view of a group: k_render_scan, k_group_reduce)
@@ -526,7 +527,7 @@ __global__ __launch_bounds__(256) void k_build_tiles(const ObjConst* oc, ObjStat
                 const bool good = status == DSP_STATUS_GOOD;
                 if (!jac) {
                     n = good ? (mode == 0 ? s.V : s.P) : 0;
-                    if ((apply_few & 2) && mode == 2) st[b].P = 0;      // a front-to-back pass's count (k_scan_rays): consumed; k_band_wave counts from zero
+                    if ((apply_few & 2) && mode == 2 && status != DSP_STATUS_DONE) st[b].P = 0;      // a front-to-back pass's count (k_scan_rays): consumed; k_band_wave counts from zero
                     off = c.samp_off;
                     cnt += n;
                     if (good) vtot += s.V;
@@ -898,8 +899,9 @@ __global__ __launch_bounds__(WAVE_THREADS) void k_render_tail_wave(const ObjCons
 #pragma unroll
     for (int w = 0; w < WAVE_RAYS; ++w) { pre += part[0][w]; ktot += part[1][w]; mtot += part[2][w]; }
     const int status = st[b].status;
-    // (an object that is not part of a partial re-run keeps its state untouched -- K and m included: launch_init_state, run_mask)
-    if (blockIdx.x == 0 && tid == 0 && status != DSP_STATUS_SKIP) { st[b].K = ktot; st[b].m = mtot; }
+    // (an object that is not part of a partial re-run keeps its state untouched -- K and m included: launch_init_state, run_mask; so does
+    // one the convergence rule has frozen)
+    if (blockIdx.x == 0 && tid == 0 && status != DSP_STATUS_SKIP && status != DSP_STATUS_DONE) { st[b].K = ktot; st[b].m = mtot; }
     if (status != DSP_STATUS_GOOD) return;
     for (int q = 0; q < TAIL_RAYS / WAVE_RAYS; ++q) {
         const int rl = wave * (TAIL_RAYS / WAVE_RAYS) + q, r = r0 + rl;
@@ -934,7 +936,7 @@ __global__ __launch_bounds__(256) void k_sum_m(const ObjConst* oc, ObjState* st,
         if (threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
         __syncthreads();
     }
-    if (threadIdx.x == 0) st[b].m = part[0];
+    if (threadIdx.x == 0 && st[b].status != DSP_STATUS_DONE) st[b].m = part[0];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1286,7 +1288,8 @@ __global__ __launch_bounds__(64) void k_group_broadcast(const GroupEnt* grp, Obj
     ObjState& s = st[b];
     const int lst = l.status;
     if (lst == DSP_STATUS_SKIP) return;
-    if (lst != DSP_STATUS_GOOD) { if (lane == 0) s.status = lst; return; }
+    // (a leader the convergence rule has frozen, DSP_STATUS_DONE, freezes its members the same way: once)
+    if (lst != DSP_STATUS_GOOD) { if (lane == 0 && s.status != lst) s.status = lst; return; }
     float nt[16];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1346,11 +1349,14 @@ template <bool V> struct BoolC { static constexpr bool value = V; };
 // GROUPS (multi-view batches): only a group's leader solves, with the group's pooled Gram sums (k_group_reduce) and its M and K from gmk;
 // GROUPS = false is the code of every other batch, untouched by the group form (a template argument, not a run-time test: k_solve sits on
 // the detection's latency path).
-template <bool GROUPS>
+// STOP (dsp_batch_convergence): the convergence rule (StopRule) is evaluated on the step this launch applies, and an object that meets it
+// is frozen: status DSP_STATUS_DONE, which every kernel of the run's remaining launches treats like a failed object (no work, no writes)
+// and k_finalize reports as good.  STOP = false is the code of every run without a rule -- a template argument like GROUPS, for the same reason.
+template <bool GROUPS, bool STOP>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int iter,
                                                          const float* codew, const float* cb0, const float* cblat, float* cbias,
                                                float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj,
-                                               const GroupEnt* grp, const int* gmk) {
+                                               const GroupEnt* grp, const int* gmk, StopRule stop) {
     __shared__ double A[NS1][NS1 + 1];          // [H | b] in rows 0..n-1 (b = column n); b is also kept as ROW n (rows 64 .. 71 are one register of the elimination)
     const int b = blockIdx.x, tid = threadIdx.x;
     if constexpr (GROUPS) { if (grp[b].leader != b) return; }
@@ -1611,6 +1617,16 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         float* tr = trace + ((size_t)iter * n_obj + b) * TRACE_STRIDE;
         for (int e = tid; e < n; e += SOLVE_THREADS) tr[NSOLVE * NSOLVE + NSOLVE + e] = (float)A[e][n];
     }
+    // the convergence rule, on the step the update below applies (lr dx; pose-only: dx): thread i < n holds entry i
+    bool stop_now = false;
+    if constexpr (STOP) {
+        bool ok = true;
+        if (tid < n) {
+            const double step = fabs((double)(prm.pose_only ? 1.f : prm.lr) * A[tid][n]);
+            ok = step < (tid < pd ? stop.pose_tol : stop.code_tol);        // strict, and false for a NaN step
+        }
+        stop_now = __syncthreads_and(ok) && iter + 1 >= stop.min_iterations;
+    }
     // 3. update (optimizer.py:187-192 / 73-74).  Wave 0 carries the pose (one lane: exp map, 4x4 product, the next iteration's derived
     //    state -- a few us of serial fp64), wave 1 the code, and waves 2.. the next iteration's code bias once the code is in LDS: the
     //    serial pose work no longer sits in front of the bias loop.
@@ -1648,12 +1664,15 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
             for (int i = 0; i < 16; ++i) s.t_oc[i] = nt[i];
             s.vsum = 0; s.ksum = 0;
             s.V = 0; s.P = 0;      // the wave-per-ray bookkeeping counts into these (k_front_wave, k_band_wave); the scans of the other forms overwrite them
+            s.n_iter = iter + 1;   // updates applied (dsp_batch_iterations_used)
         }
+        if constexpr (STOP) { if (prm.pose_only && stop_now && tid == 0) s.status = DSP_STATUS_DONE; }
         if (!prm.pose_only) {
             const IterDerived r = derive_iter_core(nt, prm.n_depth);
             if (!r.ok) {
                 if (tid == 0) s.status = DSP_STATUS_NAN;
             } else {
+                if constexpr (STOP) { if (stop_now && tid == 0) s.status = DSP_STATUS_DONE; }
                 if (tid == 0) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) s.t_co[i] = r.t_co[i];
@@ -1686,7 +1705,7 @@ __global__ void k_inlier_filter(const ObjConst* oc, ObjState* st, const float* j
     const int b = blockIdx.y;
     const ObjConst c = oc[b];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c.n_pts) return;
+    if (i >= c.n_pts || st[b].status == DSP_STATUS_DONE) return;     // frozen before this iteration: a run that short never reaches the filter
     const int idx = c.jsdf_off + i;
     const bool keep = alive[idx] && fabsf(jgrad[(size_t)idx * GRAD_STRIDE + 67]) <= 0.05f;
     alive[idx] = keep ? 1 : 0;
@@ -1695,6 +1714,7 @@ __global__ __launch_bounds__(256) void k_count_alive(const ObjConst* oc, ObjStat
     __shared__ int part[256];
     const int b = blockIdx.x;
     const ObjConst c = oc[b];
+    if (st[b].status == DSP_STATUS_DONE) return;
     int sum = 0;
     for (int i = threadIdx.x; i < c.n_pts; i += 256) sum += alive[c.jsdf_off + i];
     part[threadIdx.x] = sum;
@@ -1706,11 +1726,13 @@ __global__ __launch_bounds__(256) void k_count_alive(const ObjConst* oc, ObjStat
 // final result: T_co = inv(T_oc) (optimizer.py:200; 81-84 for pose-only, which also divides the scale out), as ONE DSP_RESULT_WIDTH row per
 // object (t_cam_obj 16 | code 64 | loss | status): what dsp_batch_results unpacks and what the multi-GPU gather sends, device-resident.
 // guard_out (optional): the always-on prepass guard's per-object words {lp_delta, trips, max error bits}, packed for the run's ONE read-back.
-__global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int pose_only, float* out_packed, unsigned* guard_out, const GroupEnt* grp) {
+__global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int pose_only, float* out_packed, unsigned* guard_out, const GroupEnt* grp,
+                           unsigned* iters_out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_obj) return;
     const ObjState& s = st[b];
-    if (s.status == DSP_STATUS_SKIP) return;      // partial re-run: the row of the earlier run stands
+    if (s.status == DSP_STATUS_SKIP) return;      // partial re-run: the row (and the iteration count) of the earlier run stands
+    if (iters_out) iters_out[b] = (unsigned)s.n_iter;
     if (guard_out) {
         guard_out[3 * b + 0] = __float_as_uint(s.lp_delta);
         guard_out[3 * b + 1] = s.guard_trips;
@@ -1731,7 +1753,7 @@ __global__ void k_finalize(ObjState* st, const float* scale_in, int n_obj, int p
     }
     for (int i = 0; i < CODE_LEN; ++i) row[16 + i] = s.code[i];
     row[80] = s.loss;
-    row[81] = (float)s.status;
+    row[81] = (float)(s.status == DSP_STATUS_DONE ? DSP_STATUS_GOOD : s.status);      // converged and frozen: a good object
 }
 
 // per-object code contribution to layer 0 and to the latent_in layer (one workgroup per object):
@@ -1848,16 +1870,19 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 }
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
-                  const GroupEnt* grp, int* gmk) {
+                  const GroupEnt* grp, int* gmk, const StopRule* stop) {
+    const StopRule rule = stop ? *stop : StopRule{0.0, 0.0, 1};
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
     if (!grp) {
-        hipLaunchKernelGGL(k_solve<false>, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
-                           (const GroupEnt*)nullptr, (const int*)nullptr);
+        auto k = stop ? k_solve<false, true> : k_solve<false, false>;
+        hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rule);
         return;
     }
     hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B);
-    hipLaunchKernelGGL(k_solve<true>, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
-                       (const int*)gmk);
+    auto k = stop ? k_solve<true, true> : k_solve<true, false>;
+    hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
+                       (const int*)gmk, rule);
     launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
 }
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
@@ -1867,8 +1892,9 @@ void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, 
     hipLaunchKernelGGL(k_inlier_filter, GRID2(maxM, B), dim3(256), 0, s, oc, st, jgrad, alive);
     hipLaunchKernelGGL(k_count_alive, dim3(B), dim3(256), 0, s, oc, st, alive);
 }
-void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out, hipStream_t s, const GroupEnt* grp) {
-    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, st, scale, B, pose_only, packed, guard_out, grp);
+void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out, hipStream_t s, const GroupEnt* grp,
+                     unsigned* iters_out) {
+    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, st, scale, B, pose_only, packed, guard_out, grp, iters_out);
 }
 
 // Testing (dsp_debug_lie): the Lie-group maps and the rotation prior exactly as k_solve evaluates them -- ONE thread, the same device

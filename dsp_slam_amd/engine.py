@@ -110,6 +110,20 @@ class Batch(object):
         L.check(L.load().dsp_batch_set_iterations(self._h, int(n)), self.engine._h, "dsp_batch_set_iterations")
         self.iters = int(n)
 
+    # ---- convergence rule (NOT one of the "identical results" settings: an object stopped after n updates returns a run of n iterations) ------
+    def set_convergence(self, pose_tol, code_tol, min_iterations=1):
+        """Freeze each object once its Gauss-Newton step is small (dsp_batch_convergence): after the update of iteration e, converged when
+        e + 1 >= min_iterations, max |lr dx_pose| < pose_tol and max |lr dx_code| < code_tol (strict; inf switches a half off; code_tol is
+        ignored by pose-only batches).  (0, 0, 1) = off, the initial state."""
+        L.check(L.load().dsp_batch_convergence(self._h, float(pose_tol), float(code_tol), int(min_iterations)), self.engine._h,
+                "dsp_batch_convergence")
+
+    def iterations_used(self):
+        """Updates applied to each object in the last run (dsp_batch_iterations_used): int32 (n,), per object also for multi-view batches."""
+        out = np.zeros(self.n, np.int32)
+        L.check(L.load().dsp_batch_iterations_used(self._h, L.ptr(out, L.c_i32p)), self.engine._h, "dsp_batch_iterations_used")
+        return out
+
     # ---- testing: pin one of the bit-identical forms the library chooses between by itself (dsp_batch_set_debug) --------------------------
     def set_debug(self, key, value):
         L.check(L.load().dsp_batch_set_debug(self._h, int(key), int(value)), self.engine._h, "dsp_batch_set_debug(%d, %d)" % (key, value))
@@ -601,14 +615,17 @@ class Engine(object):
         set_start_state(t_obj_cam) work on it; results()[0] is estimate_pose_batch's output, bit for bit."""
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
-    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32):
-        """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute)."""
+    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None):
+        """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
+        convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             return (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
         b = Batch(self, prm, t_cam_obj, pts, rays, depth, codes)
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
+            if convergence is not None:
+                b.set_convergence(*convergence)
             b.run()
             return b.results()
         finally:
@@ -618,11 +635,20 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None):
-        """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object."""
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None):
+        """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
+        convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call."""
         n = len(views)
         if n == 0:
             return (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+        if convergence is not None:
+            b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
+            try:
+                b.set_convergence(*convergence)
+                b.run()
+                return b.results()
+            finally:
+                b.close()
         vo, t_ref, pts, rays, depth = _flatten_views(views)
         (po, p), (ro, r), (do, d) = _ragged(pts, 3), _ragged(rays, 3), _ragged(depth, 0)
         t = L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_cam_obj]))
@@ -636,10 +662,20 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None):
+        """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
+        one-shot call."""
         n = len(pts)
         if n == 0:
             return np.zeros((0, 4, 4), np.float32)
+        if convergence is not None:
+            b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
+            try:
+                b.set_convergence(*convergence)
+                b.run()
+                return b.results()[0]
+            finally:
+                b.close()
         po, p = _ragged(pts, 3)
         t = L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_co_se3]))
         sc = L.f32(np.asarray(scale, np.float32).reshape(n))

@@ -49,6 +49,24 @@ class Optimizer(object):
         if dt not in ("f32", "f16", "bf16"):
             raise ValueError("optimizer.compute_dtype must be f32, f16 or bf16 (got %r)" % (dt,))
         self.compute = {"f32": _L.COMPUTE_F32, "f16": _L.COMPUTE_F16, "bf16": _L.COMPUTE_BF16}[dt]
+        # ADDITION (not in the reference's configs): "pose_tolerance" / "code_tolerance" under "joint_optim" and "pose_tolerance" under
+        # "pose_only_optim" switch the per-object convergence rule on (dsp_batch_convergence: an object stops iterating once its step is
+        # below the tolerances).  Read with a membership test -- the reference's config dict raises on a missing key -- and absent means off:
+        # every object runs every iteration, as in the reference.  One joint tolerance alone leaves the other half of the rule off (inf).
+        def optional(block, key):
+            try:
+                return float(block[key]) if key in block else None
+            except TypeError:
+                return None
+        jp, jc = optional(joint, "pose_tolerance"), optional(joint, "code_tolerance")
+        self.convergence_joint = None if jp is None and jc is None else (float("inf") if jp is None else jp, float("inf") if jc is None else jc)
+        pp = None
+        try:
+            if "pose_only_optim" in optim_cfg:
+                pp = optional(optim_cfg["pose_only_optim"], "pose_tolerance")
+        except TypeError:
+            pp = None
+        self.convergence_pose_only = None if pp is None else (pp, 0.0)
 
     def _params(self):
         return _engine.gn_params(self.k1, self.k2, self.k3, self.k4, self.b1, self.b2, self.lr, self.s_damp,
@@ -58,8 +76,9 @@ class Optimizer(object):
     # ---- pose only (reference optimizer.py:45-86) ---------------------------------------------------
     def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes):
         """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses."""
+        kw = {} if self.convergence_pose_only is None else {"convergence": self.convergence_pose_only}
         return self.decoder.engine.estimate_pose_batch(self._params(), [_f32(t) for t in t_co_se3_list], scales,
-                                                       [_f32(p) for p in pts_list], [_f32(c) for c in codes])
+                                                       [_f32(p) for p in pts_list], [_f32(c) for c in codes], **kw)
 
     def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code):
         """Pose-only refinement of one detection (reference optimizer.py:45-86; called from LocalMapping_util.cc:109-110).
@@ -75,9 +94,10 @@ class Optimizer(object):
         codes_in = None
         if codes is not None:
             codes_in = [np.zeros(self.code_len, np.float32) if c is None else _f32(c)[:self.code_len] for c in codes]
+        kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
         t, code, loss, status = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
-            [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute)
+            [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)
         out = []
         for i in range(B):
             if status[i] == _L.OBJ_GOOD:
@@ -108,7 +128,8 @@ class Optimizer(object):
         Same result dict as reconstruct_object; one view gives reconstruct_object's result, bit for bit."""
         vs = [dict(t_ref_cam=_f32(v["t_ref_cam"]), pts=_f32(v["pts"]), rays=_f32(v["rays"]), depth=_f32(v["depth"]).reshape(-1)) for v in views]
         codes_in = None if code is None else [_f32(code)[:self.code_len]]
-        t, z, loss, status = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in)
+        kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
+        t, z, loss, status = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
         if status[0] == _L.OBJ_GOOD:
             return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])))
         return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[0]))

@@ -336,6 +336,28 @@ int dsp_prepass_calibration_table(dsp_handle* h, int dtype, float* mags, float* 
  * decoder's calibration. */
 int dsp_prepass_reset_guard(dsp_handle* h);
 
+/* ---- convergence rule (optional; NOT one of the settings above: a run with it returns, per object, the result of a SHORTER run) ------------
+ * By default every object runs the batch's iteration count, as the reference does.  With a rule set, the solve step of iteration e (0-based)
+ * evaluates in fp64, on the update it has just applied,
+ *     sp = max_i |lr dx[i]| over the pose entries (7 for Sim(3); a pose-only batch: 6, and lr = 1 there, optimizer.py:73-74),
+ *     sc = max_i |lr dx[P + i]| over the code entries (absent for pose-only batches: code_tol is ignored),
+ * and the object has CONVERGED when e + 1 >= min_iterations, sp < pose_tol and sc < code_tol.  Both comparisons are strict: a tolerance of 0
+ * stops nothing, a NaN step never passes, +inf switches that half of the rule off.  A converged object keeps the update just applied and is
+ * frozen for the rest of the run: the remaining iterations decode, scan and solve nothing for it.  Objects are independent, so an object
+ * stopped after n updates returns BIT FOR BIT what a run of n iterations returns for it -- pose, code, status (DSP_OBJ_GOOD) and loss (that of
+ * its last linearisation); trace rows of iterations it did not run are zeros.  A multi-view object converges as one, decided on its pooled
+ * system.  A pose-only object frozen before the update of iteration 4 keeps all its points (the inlier filter never sees it, as in a run of
+ * <= 5 iterations).  (0, 0, 1) is the initial state and means off.  DSP_E_ARG (the previous rule stays): a negative or NaN tolerance,
+ * min_iterations < 1.  Works on joint, pose-only and multi-view batches, in fp32 and in the low-precision compute mode; the partial re-run
+ * after a prepass-guard trip uses the same rule.  The one-shot calls (dsp_reconstruct_batch, ...) always run every iteration.
+ * (Not named dsp_batch_set_*: that family is the settings above, and ABI 6 fixes its members.) */
+int dsp_batch_convergence(dsp_batch* b, float pose_tol, float code_tol, int32_t min_iterations);
+/* out[i] (n_objects entries; a multi-view batch: per object, not per view) = Gauss-Newton updates applied to object i in the last run: the
+ * iteration count without a rule; for an object that ended DSP_OBJ_FEW_SAMPLES / DSP_OBJ_NAN the updates applied before it failed; for an object
+ * left out of the partial re-run after a guard trip, the value of the run that produced its row.  Host data of the run's one read-back: no device
+ * access.  DSP_E_STATE before the first run. */
+int dsp_batch_iterations_used(dsp_batch* b, int32_t* out);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */

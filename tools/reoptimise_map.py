@@ -19,6 +19,9 @@ as one dsp_batch on its own handle from its own host thread, and the result rows
 (is_good False) or that have no observation keep their saved pose and code.  The map is written back in the reference's format.
 
     python tools/reoptimise_map.py --config configs/config_kitti.json --map_dir map/kitti/07 [--gpus N] [--out MapObjects.reopt.txt]
+
+--tol POSE CODE (off without the flag) lets every object stop once its Gauss-Newton step is below the tolerances (dsp_batch_convergence).  The
+iterations each object used are printed: how many a warm start saves depends on the map (profiles/early_stop.md).
 """
 import argparse
 import os
@@ -67,10 +70,21 @@ def object_views(ob):
     return views
 
 
-def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
+def iterations_histogram(iters):
+    """'mean M over N objects; n: count, ...' of the iterations the observed objects used."""
+    iters = np.asarray(iters, np.int64).reshape(-1)
+    if iters.size == 0:
+        return "no observed objects"
+    vals, cnt = np.unique(iters, return_counts=True)
+    return "mean %.2f over %d objects; %s" % (float(iters.mean()), iters.size, ", ".join("%d: %d" % (v, c) for v, c in zip(vals, cnt)))
+
+
+def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
-    compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute)."""
+    compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
+    tol: None, or (pose_tol, code_tol[, min_iterations]): the per-object convergence rule; stats["iterations_used"] then holds the updates applied
+    to every observed object (None without tol)."""
     from dsp_slam_amd import distributed as D
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
@@ -83,6 +97,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
         shards = D.shard_objects([sum(D.object_cost(v["pts"].shape[0], v["rays"].shape[0], prm.num_depth_samples) for v in views[i]) for i in idx],
                                  len(engines))
     parts = [None] * len(shards)
+    used = [None] * len(shards)
     multiview = any("more_views" in obs[i] for i in idx)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
@@ -91,6 +106,21 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
+        if tol is not None and b > a:      # the rule lives on resident batches: one per shard, created and destroyed here
+            if multiview:
+                bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
+            else:
+                bt = eng.batch(prm, t_in[a:b], [obs[i]["pts"] for i in sel], [obs[i]["rays"] for i in sel], [obs[i]["depth"] for i in sel], codes_in[a:b])
+            try:
+                if compute != 0:
+                    bt.set_compute(compute)
+                bt.set_convergence(*tol)
+                bt.run()
+                parts[r] = D.pack_results(*bt.results())
+                used[r] = bt.iterations_used()
+            finally:
+                bt.close()
+            return
         if multiview:      # one-view objects of such a map go through the same call: one view IS reconstruct_batch, bit for bit
             parts[r] = D.pack_results(*eng.reconstruct_multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b]))
             return
@@ -116,7 +146,9 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0):
         out[i]["pose"] = obs[i]["t_world_cam"] @ t[k].astype(np.float64)
         out[i]["code"] = codes[k, :len(objs[i]["code"])].astype(np.float32)
         out[i]["loss"] = float(loss[k])
-    return out, dict(n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed)
+    iters = None if tol is None else np.concatenate([u for u in used if u is not None] + [np.zeros(0, np.int32)])
+    return out, dict(n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
+                     iterations_used=iters)
 
 
 def main():
@@ -127,6 +159,8 @@ def main():
     ap.add_argument("--out", default=None, help="default: <map_dir>/MapObjects.reopt.txt")
     ap.add_argument("--compute", choices=("f32", "f16", "bf16"), default="f32",
                     help="f32 = the parity path (default); f16 / bf16 = the opt-in low-precision compute mode: ~3.7 x the objects/s on large maps, accuracy in profiles/r06_lp_compute.md")
+    ap.add_argument("--tol", type=float, nargs=2, metavar=("POSE", "CODE"), default=None,
+                    help="stop each object once its Gauss-Newton step is below these tolerances (pose entries / code entries); off without the flag")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -138,11 +172,14 @@ def main():
     n_dev = args.gpus or max(1, L.load().dsp_device_count())
     decoders = [config_decoder(cfg.DeepSDF_DIR).cuda(d) for d in range(n_dev)]        # one decoder (= one handle, one stream) per GPU
     prm = E.params_from_configs(cfg)
-    out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute])
+    out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute],
+                         tol=None if args.tol is None else tuple(args.tol))
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
         st["n_good"], st["n_objects"], st["n_observed"], n_dev, st["seconds"], st["n_observed"] / max(st["seconds"], 1e-9), dst))
+    if st["iterations_used"] is not None:
+        print("iterations used: %s" % iterations_histogram(st["iterations_used"]))
 
 
 if __name__ == "__main__":

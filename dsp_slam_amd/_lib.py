@@ -23,6 +23,8 @@ PREPASS_OFF, PREPASS_F16, PREPASS_BF16 = 0, 1, 2
 MESH_REGULAR_GRID, MESH_PREPASS_F16, MESH_PREPASS_BF16 = 1, 2, 4     # dsp_extract_mesh(es) flags
 PREPASS_SMALL_TILES = 0x100
 COMPUTE_F32, COMPUTE_F16, COMPUTE_BF16 = 0, 1, 2
+POSTERIOR_MEAN, POSTERIOR_SUM = 0, 1                       # dsp_batch_posterior: weights
+POSTERIOR_OK, POSTERIOR_NONE, POSTERIOR_SINGULAR = 0, 1, 2     # ... the record's status
 # keys of dsp_batch_set_debug (include/dsp_gn.h: DSP_DBG_*)
 (DBG_MASK_REUSE, DBG_SPLIT_ROWS, DBG_TAIL_SPLIT, DBG_WAVE_BOOKKEEPING, DBG_SPECULATIVE_BAND, DBG_MIXED_REUSE, DBG_CLUSTER_TILES, DBG_DIRECT_TILES,
  DBG_PREPASS_TILE, DBG_PREPASS_AUDIT, DBG_CLUSTER_FAULT, DBG_LP_SMALL_BATCHES) = range(1, 13)
@@ -95,6 +97,8 @@ SYMBOLS = [
     ("dsp_batch_set_compute", C.c_int, [_VP, C.c_int]),
     ("dsp_batch_convergence", C.c_int, [_VP, C.c_float, C.c_float, C.c_int32]),
     ("dsp_batch_iterations_used", C.c_int, [_VP, c_i32p]),
+    ("dsp_batch_posterior", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("dsp_batch_posterior_fetch", C.c_int, [_VP, c_i32p, c_f64p, c_f64p, c_f64p, c_f32p, c_i64p, c_i64p, c_i64p, c_f64p, c_f64p, c_f32p, c_f32p, c_f32p]),
     ("dsp_sdf_jacobian_lp", C.c_int, [_VP, C.c_int, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p]),
     ("dsp_batch_set_debug", C.c_int, [_VP, C.c_int, C.c_int]),
     ("dsp_prepass_calibration", C.c_int, [_VP, C.c_int, c_f32p, c_f32p]),
@@ -138,6 +142,8 @@ SYMBOLS = [
     ("dsp_pg_edge_error", C.c_int, [C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p]),
     ("dsp_pg_edge_linearize", C.c_int, [C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p]),
     ("dsp_pg_edge_chi2", C.c_int, [C.c_int64, c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
+    ("dsp_pg_edge_information", C.c_int, [C.c_int64, C.c_int, c_f64p, c_f64p, C.c_double, c_f64p]),
+    ("dsp_pg_edge_chi2_info", C.c_int, [C.c_int64, c_f64p, c_f64p, C.c_double, c_f64p, c_f64p, c_f64p]),
     ("dsp_pg_vertex_oplus", C.c_int, [C.c_int64, C.c_int, c_f64p, c_f64p, c_f64p]),
     # test hook, not in dsp_gn.h: the launch plan of one row of inputs, on the host (tests/test_launch_plan.py)
     ("dsp_debug_launch_plan", C.c_int, [c_i32p, C.c_int, c_i32p, C.c_int]),

@@ -355,6 +355,14 @@ void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, doubl
 // -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
 void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s);
+// posterior pass (dsp_batch_posterior).  launch_posterior_park: every member's status word into park[], frozen objects (DSP_STATUS_DONE) take
+// part as good ones.  launch_posterior: launch_solve's reductions (no trace), then k_posterior: one record of rec_stride doubles per OBJECT
+// (POSTERIOR_REC_L1, or _L2 with Lambda, g and the state), and the parked status words go back.  weights: DSP_POSTERIOR_MEAN / _SUM.
+constexpr int POSTERIOR_REC_L1 = 168;
+constexpr int POSTERIOR_REC_L2 = POSTERIOR_REC_L1 + 71 * 71 + 71 + (16 + CODE_LEN + MAX_DEPTH_SAMPLES) / 2;
+void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
+void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
+                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
 void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,
                      const GroupEnt* grp = nullptr, unsigned* iters_out = nullptr /*optional B: ObjState::n_iter*/);   // grp: one row per OBJECT, written by the group's leader

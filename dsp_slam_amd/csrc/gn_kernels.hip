@@ -1700,6 +1700,226 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// posterior pass (dsp_batch_posterior): one more linearisation at the state the run RETURNS, turned into a marginal
+// ------------------------------------------------------------------------------------------------
+// In front of the pass: every member's status word is parked, and an object the convergence rule froze (DSP_STATUS_DONE) takes part in
+// the pass as a good one.  k_posterior puts the parked words back, so that k_finalize reads what it reads without the pass.
+__global__ void k_posterior_park(ObjState* st, int* park, int n_obj) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_obj) return;
+    const int s0 = st[b].status;
+    park[b] = s0;
+    if (s0 == DSP_STATUS_DONE) st[b].status = DSP_STATUS_GOOD;
+}
+
+// One workgroup per object (multi-view: the leader's; it also restores its members' status words).  Lambda and g are assembled from the
+// fp64 Gram sums exactly as k_solve assembles H and b -- same expressions, same order of additions -- without the damping, and with the
+// caller's weights (weights 0: k2 / M, k1 / K; 1: k2, k1).  The lower triangle is computed and mirrored.  Then the symmetric sweep operator,
+// pivot-free, on the live unknowns n_act = pose + the decoder's code length, code block FIRST: for pivot k with d = a_kk, rd = 1 / d and
+// c_i = a_ik,
+//     a_ij <- fma(-(c_i rd), c_j, a_ij)  (i >= j, both != k),   a_ik = a_ki <- c_i rd,   a_kk <- -rd
+// -- every entry is ONE fma per step from the column as it stood before the step, so the kernel is emulated entry for entry
+// (tests/posterior_ref.py).  After the code pivots the pose block IS the Schur complement Lambda_pp - Lambda_pc Lambda_cc^-1 Lambda_cp
+// (info_pose); after the pose pivots the matrix is -Lambda^-1 (var_code; cov_pose after one refinement step against Lambda, below).  A pivot that is not greater than 16 FLT_EPSILON times
+// its own original diagonal entry is round-off of the fp32 Gram chains: DSP_POSTERIOR_SINGULAR.
+// Record (doubles, rec_stride apart): info P x P @0 | cov P x P @49 | var_code 64 @98 | status, loss, M, V, K @162 | level 2: Lambda 71 x 71 @168 |
+// g 71 | then as floats: t_oc 16, code 64, depths 64.
+constexpr int POST_L1 = POSTERIOR_REC_L1;
+static_assert(POSTERIOR_REC_L2 == POST_L1 + NSOLVE * NSOLVE + NSOLVE + (16 + CODE_LEN + MAX_DEPTH_SAMPLES) / 2, "posterior record layout");
+constexpr int POST_THREADS = 1024;
+template <bool GROUPS>
+__global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int weights, int level,
+                                                            const int* park, const GroupEnt* grp, const int* gmk, double* rec, int rec_stride) {
+    __shared__ double A[NSOLVE][NSOLVE + 1];
+    __shared__ double s_c[NSOLVE + 1], s_d0[NSOLVE + 1];
+    __shared__ int s_sing;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int n_mem = 1, row_i = b;
+    if constexpr (GROUPS) {
+        const GroupEnt g = grp[b];
+        if (g.leader != b) return;
+        n_mem = g.n_members; row_i = g.object;
+    }
+    const int parked = park[b];
+    if (parked == DSP_STATUS_SKIP) return;           // partial re-run: the record of the earlier run stands, like the result row
+    ObjState& s = st[b];
+    const ObjConst c = oc[b];
+    const int status = s.status;
+    double* out = rec + (size_t)row_i * rec_stride;
+    const int pd = prm.pose_only ? 6 : 7;
+    const int n = prm.pose_only ? 6 : pd + prm.code_len;       // live unknowns: the leading n x n block
+    int M = c.n_pts, K = s.K, V = s.V;
+    if constexpr (GROUPS) {
+        M = gmk[2 * b]; K = gmk[2 * b + 1];
+        V = 0;
+        for (int v = 0; v < n_mem; ++v) if (st[b + v].status == DSP_STATUS_GOOD) V += st[b + v].V;
+    }
+    if (prm.pose_only) { M = (s.n_alive >= 0) ? s.n_alive : M; K = 0; V = 0; }
+    const double* G0p = gsum + ((size_t)b * 2 + 0) * (72 * 72);
+    const double* G1p = gsum + ((size_t)b * 2 + 1) * (72 * 72);
+    // status of the record; the loss at x* in k_solve's float32 arithmetic
+    int pstat = 0;
+    float loss = 0.f;
+    if (status != DSP_STATUS_GOOD) pstat = 1;
+    else if (prm.pose_only) { if (M == 0) pstat = 1; }
+    else if (M == 0 || K == 0) pstat = 1;
+    else {
+        const double g_loss0 = G0p[71 * 72 + 71], g_loss1 = G1p[71 * 72 + 71];
+        const float sdf_loss = (float)g_loss0 / (float)M;
+        const float ren_loss = (float)g_loss1 / (float)K;
+        if (isnan(sdf_loss) || isnan(ren_loss)) pstat = 1;
+        else loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
+    }
+    __syncthreads();          // every thread has read the status words: put the parked ones back (the pass changes no result)
+    for (int v = tid; v < n_mem; v += POST_THREADS) st[b + v].status = park[b + v];
+    // the state the record is taken at
+    if (level >= 2) {
+        float* fs = reinterpret_cast<float*>(out + POST_L1 + NSOLVE * NSOLVE + NSOLVE);
+        if (tid < 16) fs[tid] = s.t_oc[tid];
+        if (tid < CODE_LEN) fs[16 + tid] = s.code[tid];
+        if (tid < MAX_DEPTH_SAMPLES) fs[16 + CODE_LEN + tid] = prm.pose_only ? 0.f : s.depths[tid];
+    }
+    if (pstat) {              // uniform
+        for (int e = tid; e < (level >= 2 ? POST_L1 + NSOLVE * NSOLVE + NSOLVE : POST_L1); e += POST_THREADS) out[e] = 0.0;
+        __syncthreads();
+        if (tid == 0) { out[162] = (double)pstat; out[164] = (double)M; out[165] = (double)V; out[166] = (double)K; }
+        return;
+    }
+    // 1. Lambda (lower triangle, mirrored) and g
+    float jrot3 = 0.f, jrot5 = 0.f, res_rot = 0.f;
+    double w_s = 0.0, w_r = 0.0;
+    if (!prm.pose_only) {
+        float pr_tco[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) pr_tco[i] = s.t_co[i];
+        float jrot[7];
+        rotation_prior(pr_tco, s.scale, jrot, res_rot);
+        jrot3 = jrot[3]; jrot5 = jrot[5];
+        w_s = weights ? (double)prm.k2 : (double)prm.k2 / (double)M;
+        w_r = weights ? (double)prm.k1 : (double)prm.k1 / (double)K;
+    }
+    auto jr = [=](int i) { return i == 3 ? jrot3 : (i == 5 ? jrot5 : 0.f); };
+    // entry (i, j), i >= j, of Lambda from the Gram sums (also re-read by the refinement of cov_pose below: the sweeps overwrite A)
+    auto lam = [&](int i, int j) -> double {
+        if (prm.pose_only) {
+            double v = G0p[i * 72 + j];
+            if (!weights) v = v / (double)M;
+            return v;
+        }
+        const double g0 = G0p[i * 72 + j], g1 = G1p[i * 72 + j];
+        double v = w_s * g0 + w_r * g1;
+        if (i >= pd && i == j) v += (double)prm.k3;
+        if (i < pd && j < pd) v += (double)prm.k4 * (double)jr(i) * (double)jr(j);
+        return v;
+    };
+    if (!prm.pose_only) {
+        for (int e = tid; e < n * (n + 1); e += POST_THREADS) {
+            const int i = e / (n + 1), j = e % (n + 1);
+            if (j < n) {
+                if (j > i) continue;
+                const double v = lam(i, j);
+                A[i][j] = v;
+                A[j][i] = v;
+            } else {
+                const double g0 = G0p[i * 72 + 71], g1 = G1p[i * 72 + 71];
+                double v = -(w_s * g0 + w_r * g1);
+                if (i >= pd) v -= (double)prm.k3 * (double)s.code[i - pd];
+                if (i < pd) v += (double)prm.k4 * (double)jr(i) * (double)res_rot;
+                s_c[i] = v;
+            }
+        }
+    } else {
+        for (int e = tid; e < n * (n + 1); e += POST_THREADS) {
+            const int i = e / (n + 1), j = e % (n + 1);
+            if (j < n) {
+                if (j > i) continue;
+                const double v = lam(i, j);
+                A[i][j] = v;
+                A[j][i] = v;
+            } else {
+                double v = -G0p[i * 72 + 71];
+                if (!weights) v = v / (double)M;
+                s_c[i] = v;
+            }
+        }
+    }
+    if (tid == 0) s_sing = 0;
+    __syncthreads();
+    if (tid < n) s_d0[tid] = A[tid][tid];
+    if (level >= 2) {
+        double* L = out + POST_L1;
+        for (int e = tid; e < NSOLVE * NSOLVE; e += POST_THREADS) {
+            const int i = e / NSOLVE, j = e % NSOLVE;
+            L[e] = (i < n && j < n) ? A[i][j] : 0.0;
+        }
+        if (tid < NSOLVE) L[NSOLVE * NSOLVE + tid] = tid < n ? s_c[tid] : 0.0;
+    }
+    for (int e = tid; e < POST_L1; e += POST_THREADS) out[e] = 0.0;
+    __syncthreads();
+    if (prm.pose_only && tid < 36) out[tid] = A[tid / 6][tid % 6];        // info_pose = Lambda, also for a singular one
+    // 2. sweeps: the code block, then the pose block
+    const double tiny = 16.0 * (double)1.1920928955078125e-07f;
+    bool sing = false;
+#pragma unroll 1
+    for (int t = 0; t < n; ++t) {
+        const int k = (t < n - pd) ? pd + t : t - (n - pd);
+        if (t == n - pd && !prm.pose_only) {         // the code block is swept: the pose block is the Schur complement
+            if (tid < 49) out[tid] = A[tid / 7][tid % 7];
+        }
+        if (tid < n) s_c[tid] = A[tid][k];
+        __syncthreads();
+        const double d = s_c[k];
+        if (!(d > tiny * s_d0[k])) { sing = true; break; }          // uniform (also NaN)
+        const double rd = 1.0 / d;
+        for (int e = tid; e < n * n; e += POST_THREADS) {
+            const int i = e / n, j = e % n;
+            if (j > i) continue;
+            double v;
+            if (i == k && j == k) v = -rd;
+            else if (j == k) v = s_c[i] * rd;
+            else if (i == k) v = s_c[j] * rd;
+            else v = fma(-(s_c[i] * rd), s_c[j], A[i][j]);
+            A[i][j] = v;
+            A[j][i] = v;
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (sing) {
+        if (!prm.pose_only && tid < 49) out[tid] = 0.0;
+    } else {
+        // 3. cov_pose, refined: one Newton-Schulz step of the pose columns X_p of X = -A against Lambda itself, X_p += X (E_p - Lambda X_p),
+        //    with the residual accumulated in double-double (error-free product and sum, explicitly rounded operations: no contraction) --
+        //    inverting the 7 x 7 Schur complement by sweeps alone loses cond(info_pose) eps, which pivoted LU does not
+        __shared__ double s_R[NSOLVE][7];
+        for (int e = tid; e < n * pd; e += POST_THREADS) {
+            const int i = e / pd, c = e % pd;
+            double hi = (i == c) ? 1.0 : 0.0, lo = 0.0;
+            for (int k = 0; k < n; ++k) {
+                const double l = lam(max(i, k), min(i, k)), x = -A[k][c];
+                const double q = __dmul_rn(l, x), qe = __fma_rn(l, x, -q);            // l x = q + qe exactly
+                const double sum = __dadd_rn(hi, -q), bb = __dadd_rn(sum, -hi);
+                const double err = __dadd_rn(__dadd_rn(hi, -__dadd_rn(sum, -bb)), __dadd_rn(-q, -bb));
+                hi = sum;
+                lo = __dadd_rn(lo, __dadd_rn(err, -qe));
+            }
+            s_R[i][c] = __dadd_rn(hi, lo);
+        }
+        __syncthreads();
+        if (tid < pd * pd && tid % pd <= tid / pd) {
+            const int a = tid / pd, c = tid % pd;
+            double acc = 0.0;
+            for (int i = 0; i < n; ++i) acc = __fma_rn(-A[a][i], s_R[i][c], acc);
+            const double v = __dadd_rn(-A[a][c], acc);
+            out[49 + a * pd + c] = v;
+            out[49 + c * pd + a] = v;
+        }
+        if (tid >= 64 && tid < 64 + n - pd) out[98 + tid - 64] = -A[pd + tid - 64][pd + tid - 64];
+    }
+    if (tid == 0) { out[162] = sing ? 2.0 : 0.0; out[163] = (double)loss; out[164] = (double)M; out[165] = (double)V; out[166] = (double)K; }
+}
+
 // pose-only inlier filter at e == 4 (optimizer.py:76-78): keep |r| <= 0.05 for the following iterations
 __global__ void k_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive) {
     const int b = blockIdx.y;
@@ -1884,6 +2104,22 @@ void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, doubl
     hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
                        (const int*)gmk, rule);
     launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
+}
+void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_posterior_park, dim3((B + 63) / 64), dim3(64), 0, s, st, park, B);
+}
+void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
+                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk) {
+    // the reductions launch_solve runs (no trace row), then the record
+    hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
+    if (!grp) {
+        hipLaunchKernelGGL(k_posterior<false>, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park,
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride);
+        return;
+    }
+    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, 0, (float*)nullptr, B);
+    hipLaunchKernelGGL(k_posterior<true>, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park, grp,
+                       (const int*)gmk, rec, rec_stride);
 }
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_group_broadcast, dim3(B), dim3(64), 0, s, grp, st, cbias, depths, n_depth);

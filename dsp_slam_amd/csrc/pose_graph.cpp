@@ -259,6 +259,56 @@ int dsp_pg_edge_chi2(int64_t n, const double* err, double inv_sigma, double hube
     return DSP_OK;
 }
 
+int dsp_pg_edge_information(int64_t n, int dof, const double* info_pose, const double* scale, double gain, double* info66) {
+    if (bad(n, info_pose, scale) || (n > 0 && !info66) || (dof != 6 && dof != 7)) return DSP_E_ARG;
+    for (int64_t e = 0; e < n; ++e) {
+        const double* S = info_pose + (size_t)dof * dof * e;
+        const double sc = scale[e];
+        if (!(sc > 0.0)) return DSP_E_ARG;
+        if (dof == 7 && !(S[48] > 0.0)) return DSP_E_ARG;
+        // the optimiser's [v | w] block with sigma marginalised (Schur complement over index 6)
+        double S6[6][6];
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) S6[i][j] = dof == 7 ? S[7 * i + j] - S[7 * i + 6] * S[7 * 6 + j] / S[48] : S[6 * i + j];
+        // [omega | upsilon] = [w, s v]: rows / columns 0..2 are the optimiser's 3..5, 3..5 its 0..2 divided by s
+        double* O = info66 + 36 * e;
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) {
+                const int si = i < 3 ? i + 3 : i - 3, sj = j < 3 ? j + 3 : j - 3;
+                double v = S6[si][sj];
+                if (i >= 3) v /= sc;
+                if (j >= 3) v /= sc;
+                O[6 * i + j] = gain * v;
+            }
+    }
+    return DSP_OK;
+}
+
+int dsp_pg_edge_chi2_info(int64_t n, const double* err, const double* info66, double huber_delta, double* chi2, double* rho, double* weight) {
+    if (bad(n, err, chi2) || (n > 0 && !info66)) return DSP_E_ARG;
+    const double d2 = huber_delta * huber_delta;
+    for (int64_t e = 0; e < n; ++e) {
+        const double* er = err + 6 * e;
+        const double* O = info66 + 36 * e;
+        double e2 = 0.0;
+        for (int i = 0; i < 6; ++i) {
+            double row = 0.0;
+            for (int k = 0; k < 6; ++k) row += O[6 * i + k] * er[k];
+            e2 += er[i] * row;
+        }
+        chi2[e] = e2;
+        double r = e2, w = 1.0;
+        if (huber_delta > 0.0 && !(e2 <= d2)) {   // as dsp_pg_edge_chi2
+            const double s = std::sqrt(e2);
+            r = 2.0 * s * huber_delta - d2;
+            w = huber_delta / s;
+        }
+        if (rho) rho[e] = r;
+        if (weight) weight[e] = w;
+    }
+    return DSP_OK;
+}
+
 int dsp_pg_vertex_oplus(int64_t n, int kind, const double* estimate, const double* update, double* out) {
     if (bad(n, estimate, update) || (n > 0 && !out) || (kind != DSP_PG_VERTEX_EXPMAP && kind != DSP_PG_VERTEX_OBJECT)) return DSP_E_ARG;
     for (int64_t e = 0; e < n; ++e) {

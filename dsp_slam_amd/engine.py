@@ -124,6 +124,37 @@ class Batch(object):
         L.check(L.load().dsp_batch_iterations_used(self._h, L.ptr(out, L.c_i32p)), self.engine._h, "dsp_batch_iterations_used")
         return out
 
+    # ---- posterior (changes no result: one more linearisation at the returned state, include/dsp_gn.h) ------------------------------------
+    def set_posterior(self, level=1, weights="mean"):
+        """level 0 = off (initial), 1 = pose information / covariance, code variance, loss and counts per object, 2 = also Lambda, g and the
+        state they were taken at.  weights "mean" (the reference's objective: k2 / M, k1 / K) or "sum" (k2, k1: information grows with the
+        number of observations -- what pose_graph.edge_information wants)."""
+        L.check(L.load().dsp_batch_posterior(self._h, int(level), _posterior_weights(weights)), self.engine._h, "dsp_batch_posterior")
+        self._posterior_level = int(level)
+
+    def posterior(self):
+        """The records of the last run (dsp_batch_posterior_fetch), per object: dict(status int32 (n,) -- L.POSTERIOR_OK / _NONE / _SINGULAR,
+        info_pose / cov_pose float64 (n, P, P) with P = 7 (pose-only: 6) in the order [v, w, sigma], var_code float64 (n, code_len),
+        loss float32, M / V / K int64; after a level-2 run also Lambda (n, 71, 71), g (n, 71), t_obj_cam (n, 4, 4), code (n, code_len),
+        depths (n, 64))."""
+        n, P = self.n, 6 if self.pose_only else 7
+        lib, h = L.load(), self.engine._h
+        out = dict(status=np.zeros(n, np.int32), info_pose=np.zeros((n, P, P)), cov_pose=np.zeros((n, P, P)), var_code=np.zeros((n, L.CODE_LEN)),
+                   loss=np.zeros(n, np.float32), M=np.zeros(n, np.int64), V=np.zeros(n, np.int64), K=np.zeros(n, np.int64))
+        l1 = (L.ptr(out["status"], L.c_i32p), L.ptr(out["info_pose"], L.c_f64p), L.ptr(out["cov_pose"], L.c_f64p), L.ptr(out["var_code"], L.c_f64p),
+              L.ptr(out["loss"]), L.ptr(out["M"], L.c_i64p), L.ptr(out["V"], L.c_i64p), L.ptr(out["K"], L.c_i64p))
+        if getattr(self, "_posterior_run_level", 0) < 2:            # a level-1 run keeps no Lambda (level 0 / no run: the call says so)
+            L.check(lib.dsp_batch_posterior_fetch(self._h, *l1, None, None, None, None, None), h, "dsp_batch_posterior_fetch")
+        else:
+            l2 = dict(Lambda=np.zeros((n, 71, 71)), g=np.zeros((n, 71)), t_obj_cam=np.zeros((n, 4, 4), np.float32), code=np.zeros((n, L.CODE_LEN), np.float32),
+                      depths=np.zeros((n, 64), np.float32))
+            L.check(lib.dsp_batch_posterior_fetch(self._h, *l1, L.ptr(l2["Lambda"], L.c_f64p), L.ptr(l2["g"], L.c_f64p), L.ptr(l2["t_obj_cam"]), L.ptr(l2["code"]),
+                                                  L.ptr(l2["depths"])), h, "dsp_batch_posterior_fetch")
+            out.update(l2)
+            out["code"] = np.ascontiguousarray(out["code"][:, :self.engine.code_len])
+        out["var_code"] = np.ascontiguousarray(out["var_code"][:, :self.engine.code_len])
+        return out
+
     # ---- testing: pin one of the bit-identical forms the library chooses between by itself (dsp_batch_set_debug) --------------------------
     def set_debug(self, key, value):
         L.check(L.load().dsp_batch_set_debug(self._h, int(key), int(value)), self.engine._h, "dsp_batch_set_debug(%d, %d)" % (key, value))
@@ -220,6 +251,7 @@ class Batch(object):
 
     def run(self):
         L.check(L.load().dsp_batch_run(self._h), self.engine._h, "dsp_batch_run")
+        self._posterior_run_level = getattr(self, "_posterior_level", 0)      # what posterior() may ask dsp_batch_posterior_fetch for
 
     def results(self):
         n = self.n
@@ -265,6 +297,20 @@ class Batch(object):
             self.close()
         except Exception:
             pass
+
+
+def _posterior_weights(weights):
+    w = {"mean": L.POSTERIOR_MEAN, "sum": L.POSTERIOR_SUM, L.POSTERIOR_MEAN: L.POSTERIOR_MEAN, L.POSTERIOR_SUM: L.POSTERIOR_SUM}.get(weights)
+    if w is None:
+        raise ValueError("posterior weights must be 'mean' or 'sum', not %r" % (weights,))
+    return w
+
+
+def _posterior_args(posterior):
+    """posterior= of the Engine calls: "mean" / "sum" (level 1) or (level, weights)."""
+    if isinstance(posterior, (tuple, list)):
+        return int(posterior[0]), posterior[1]
+    return 1, posterior
 
 
 def _flatten_views(views_per_object):
@@ -615,19 +661,24 @@ class Engine(object):
         set_start_state(t_obj_cam) work on it; results()[0] is estimate_pose_batch's output, bit for bit."""
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
-    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None):
+    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, posterior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
-        convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence."""
+        convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
+        posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
+        (the first four are bit for bit those of the call without it)."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
-            return (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+            empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+            return empty if posterior is None else empty + ({},)
         b = Batch(self, prm, t_cam_obj, pts, rays, depth, codes)
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
             if convergence is not None:
                 b.set_convergence(*convergence)
+            if posterior is not None:
+                b.set_posterior(*_posterior_args(posterior))
             b.run()
-            return b.results()
+            return b.results() if posterior is None else b.results() + (b.posterior(),)
         finally:
             b.close()
 
@@ -635,18 +686,23 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None):
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None):
         """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
-        convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call."""
+        convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call.
+        posterior: as reconstruct_batch (a resident batch too; a fifth item, per object)."""
         n = len(views)
         if n == 0:
-            return (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
-        if convergence is not None:
+            empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+            return empty if posterior is None else empty + ({},)
+        if convergence is not None or posterior is not None:
             b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
             try:
-                b.set_convergence(*convergence)
+                if convergence is not None:
+                    b.set_convergence(*convergence)
+                if posterior is not None:
+                    b.set_posterior(*_posterior_args(posterior))
                 b.run()
-                return b.results()
+                return b.results() if posterior is None else b.results() + (b.posterior(),)
             finally:
                 b.close()
         vo, t_ref, pts, rays, depth = _flatten_views(views)
@@ -662,18 +718,21 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None):
         """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
-        one-shot call."""
+        one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior())."""
         n = len(pts)
         if n == 0:
-            return np.zeros((0, 4, 4), np.float32)
-        if convergence is not None:
+            return np.zeros((0, 4, 4), np.float32) if posterior is None else (np.zeros((0, 4, 4), np.float32), {})
+        if convergence is not None or posterior is not None:
             b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
             try:
-                b.set_convergence(*convergence)
+                if convergence is not None:
+                    b.set_convergence(*convergence)
+                if posterior is not None:
+                    b.set_posterior(*_posterior_args(posterior))
                 b.run()
-                return b.results()[0]
+                return b.results()[0] if posterior is None else (b.results()[0], b.posterior())
             finally:
                 b.close()
         po, p = _ragged(pts, 3)

@@ -95,6 +95,34 @@ def edge_chi2(err, inv_sigma=INV_SIGMA_OBJECT, huber_delta=0.0):
     return (chi2[0], rho[0], w[0]) if single else (chi2, rho, w)
 
 
+def edge_information(info_pose, scale, gain=1.0):
+    """(n,6,6) / (6,6) edge information in g2o's [omega | upsilon] coordinates from the optimiser's pose information (`Batch.posterior()`'s
+    `info_pose`, (n,7,7) joint or (n,6,6) pose-only; take the "sum" weights) and the objects' scales: what `edge->setInformation` gets in
+    place of `1e3 I`."""
+    a = np.ascontiguousarray(info_pose, dtype=np.float64)
+    if a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2] or a.shape[-1] not in (6, 7):
+        raise ValueError("info_pose must be (n, 7, 7), (n, 6, 6) or one such matrix")
+    single = a.ndim == 2
+    dof = a.shape[-1]
+    a = a.reshape(-1, dof * dof)
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (a.shape[0],)))
+    out = np.empty((a.shape[0], 36))
+    L.check(L.load().dsp_pg_edge_information(a.shape[0], dof, _p(a), _p(sc), float(gain), _p(out)), None, "dsp_pg_edge_information")
+    out = out.reshape(-1, 6, 6)
+    return out[0] if single else out
+
+
+def edge_chi2_info(err, info, huber_delta=0.0):
+    """(chi2, rho, weight) with a full 6 x 6 information matrix per edge; the Huber kernel as `edge_chi2`."""
+    e, single = _f64(err, 6)
+    o = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 36)
+    if o.shape[0] != e.shape[0]:
+        raise ValueError("err and info must have the same number of edges")
+    chi2, rho, w = np.empty(e.shape[0]), np.empty(e.shape[0]), np.empty(e.shape[0])
+    _call("dsp_pg_edge_chi2_info", e.shape[0], _p(e), _p(o), float(huber_delta), _p(chi2), _p(rho), _p(w))
+    return (chi2[0], rho[0], w[0]) if single else (chi2, rho, w)
+
+
 def vertex_oplus(estimate, update, kind=VERTEX_EXPMAP):
     s, single = _f64(estimate, 7)
     u, _ = _f64(update, 6)

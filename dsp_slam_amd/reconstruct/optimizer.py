@@ -67,6 +67,24 @@ class Optimizer(object):
         except TypeError:
             pp = None
         self.convergence_pose_only = None if pp is None else (pp, 0.0)
+        # ADDITION (not in the reference's configs): "posterior": "mean" | "sum" under "joint_optim" / "pose_only_optim" switches the posterior
+        # pass on (dsp_batch_posterior: pose information and covariance, code variance and the loss AT the returned state; the reference's
+        # fields stay bit for bit what they are without it).  Read with a membership test like the tolerances; absent means off.
+        def optional_weights(block, where):
+            try:
+                w = block["posterior"] if "posterior" in block else None
+            except TypeError:
+                return None
+            if w is not None and w not in ("mean", "sum"):
+                raise ValueError("optimizer.%s.posterior must be 'mean' or 'sum' (got %r)" % (where, w))
+            return w
+        self.posterior_joint = optional_weights(joint, "joint_optim")
+        self.posterior_pose_only = None
+        try:
+            if "pose_only_optim" in optim_cfg:
+                self.posterior_pose_only = optional_weights(optim_cfg["pose_only_optim"], "pose_only_optim")
+        except TypeError:
+            pass
 
     def _params(self):
         return _engine.gn_params(self.k1, self.k2, self.k3, self.k4, self.b1, self.b2, self.lr, self.s_damp,
@@ -74,9 +92,12 @@ class Optimizer(object):
                                  self.num_iterations_pose_only)
 
     # ---- pose only (reference optimizer.py:45-86) ---------------------------------------------------
-    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes):
-        """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses."""
+    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes, return_posterior=False):
+        """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses.  return_posterior=True: (poses,
+        Batch.posterior() dict) -- 6 x 6 pose information / covariance per object, with the weights of pose_only_optim.posterior ("mean" if absent)."""
         kw = {} if self.convergence_pose_only is None else {"convergence": self.convergence_pose_only}
+        if return_posterior:
+            kw["posterior"] = self.posterior_pose_only or "mean"
         return self.decoder.engine.estimate_pose_batch(self._params(), [_f32(t) for t in t_co_se3_list], scales,
                                                        [_f32(p) for p in pts_list], [_f32(c) for c in codes], **kw)
 
@@ -95,17 +116,29 @@ class Optimizer(object):
         if codes is not None:
             codes_in = [np.zeros(self.code_len, np.float32) if c is None else _f32(c)[:self.code_len] for c in codes]
         kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
-        t, code, loss, status = self.decoder.engine.reconstruct_batch(
+        if self.posterior_joint is not None:
+            kw["posterior"] = self.posterior_joint
+        res = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
             [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)
+        t, code, loss, status = res[:4]
         out = []
         for i in range(B):
             if status[i] == _L.OBJ_GOOD:
                 out.append(ForceKeyErrorDict(t_cam_obj=t[i].copy(), code=code[i].copy(), is_good=True,
-                                             loss=torch.tensor(float(loss[i]))))
+                                             loss=torch.tensor(float(loss[i])), **self._posterior_fields(res, i)))
             else:   # reference: t_cam_obj=None, code=None, is_good=False, loss=<last computed loss> (:131,136,143,150)
                 out.append(ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[i])))
         return out
+
+    def _posterior_fields(self, res, i):
+        """The extra result fields of a good object when joint_optim.posterior is set (none otherwise: the dict is the reference's four)."""
+        if self.posterior_joint is None:
+            return {}
+        post = res[4]
+        return dict(pose_information=post["info_pose"][i].copy(), pose_covariance=post["cov_pose"][i].copy(),
+                    code_variance=post["var_code"][i].copy(), loss_at_result=float(post["loss"][i]),
+                    posterior_ok=bool(post["status"][i] == _L.POSTERIOR_OK))
 
     def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None):
         """Joint shape + pose optimisation of one object (reference optimizer.py:88-203; LocalMapping_util.cc:179-180,391-392,402-403).
@@ -129,9 +162,13 @@ class Optimizer(object):
         vs = [dict(t_ref_cam=_f32(v["t_ref_cam"]), pts=_f32(v["pts"]), rays=_f32(v["rays"]), depth=_f32(v["depth"]).reshape(-1)) for v in views]
         codes_in = None if code is None else [_f32(code)[:self.code_len]]
         kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
-        t, z, loss, status = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
+        if self.posterior_joint is not None:
+            kw["posterior"] = self.posterior_joint
+        res = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
+        t, z, loss, status = res[:4]
         if status[0] == _L.OBJ_GOOD:
-            return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])))
+            return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])),
+                                     **self._posterior_fields(res, 0))
         return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[0]))
 
     @staticmethod

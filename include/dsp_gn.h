@@ -358,6 +358,44 @@ int dsp_batch_convergence(dsp_batch* b, float pose_tol, float code_tol, int32_t 
  * access.  DSP_E_STATE before the first run. */
 int dsp_batch_iterations_used(dsp_batch* b, int32_t* out);
 
+/* ---- posterior (optional): how well the data determined each object's returned pose and code ----------------------------------------------
+ * With level > 0, the run is followed by ONE more linearisation at each object's final state x* = (T_oc, z), done exactly as an iteration of
+ * the run linearises there (same sampling, depth samples derived from the pose, selection rules, Huber weights, prepass, guard and launch
+ * forms; in the low-precision compute mode, in that mode).  Unknowns are ordered as in H: [v(3), w(3), sigma | code(64)].
+ *     Lambda = w_s G_s + w_r G_r + k3 I_code + k4 J_rot J_rot^T     (fp64, assembled as the solve step assembles H, WITHOUT the damping:
+ *                                                                    no + I_7, no + s_damp -- damping is step control, not information)
+ *     g      = the solve step's right-hand side b
+ *     DSP_POSTERIOR_MEAN: w_s = k2 / M, w_r = k1 / K (the reference's objective);  DSP_POSTERIOR_SUM: w_s = k2, w_r = k1 (sums of squares:
+ *     information grows with the number of observations -- what a pose graph wants).  The priors are the same in both.
+ * Code slots beyond the decoder's code length are not unknowns (outputs 0).  Pose-only batches: Lambda = J6^T J6 w over the points alive at
+ * the end of the run (after the inlier filter if it ran), w = 1 / n_alive or 1; no 1e-2 I.  Multi-view objects: the pooled system.
+ * Per OBJECT (multi-view: per object, not per view), float64, row-major, symmetric bit for bit:
+ *     status     DSP_POSTERIOR_OK; _NONE: the object did not end the run good, or the linearisation at x* failed by the reference's rules
+ *                (< 10 in-sphere samples, K == 0, NaN); _SINGULAR: a pivot of the pivot-free fp64 elimination was not greater than
+ *                16 FLT_EPSILON times its own original diagonal entry (round-off of the fp32 Gram chains)
+ *     info_pose  P x P (P = 7, pose-only 6): the pose's marginal information, Lambda_pp - Lambda_pc Lambda_cc^-1 Lambda_cp (pose-only: Lambda,
+ *                filled also when singular)
+ *     cov_pose   P x P: its inverse, (Lambda^-1)_pp;  var_code 64: diag((Lambda^-1)_cc).  Zeros when singular, for pose-only (var_code) and unused slots
+ *     loss       k1 L_render + k2 L_sdf AT x*, in the solve step's float32 arithmetic (dsp_batch_results' loss is one update older)
+ *     M, V, K    the counts the linearisation used (pose-only: M = points alive)
+ *     level 2:   Lambda 71 x 71, g 71, and the state: t_obj_cam 16, code 64, depths 64 (float32; multi-view: the reference view's)
+ * dsp_batch_results, _iterations_used, _trace and the packed rows are bit for bit what they are with the posterior off: the pass parks and
+ * restores every status word (objects frozen by the convergence rule take part as good ones), writes no loss, iteration count or trace row,
+ * and a failure inside it is DSP_POSTERIOR_NONE, not a changed result status.  The prepass guard works in the pass as in any iteration.
+ * Level 1 costs ~1.3 KB per object in the run's one read-back, level 2 ~42 KB.  level 0 (initial) = off.  DSP_E_ARG: another level or
+ * weights value (the previous setting stays).  The one-shot calls have no posterior.  (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+#define DSP_POSTERIOR_MEAN 0
+#define DSP_POSTERIOR_SUM 1
+#define DSP_POSTERIOR_OK 0
+#define DSP_POSTERIOR_NONE 1
+#define DSP_POSTERIOR_SINGULAR 2
+int dsp_batch_posterior(dsp_batch* b, int level /* 0 off (initial), 1, 2 */, int weights);
+/* The records of the last run (host data of its read-back: no device access); an object left out of the partial re-run after a guard trip
+ *  keeps its record like its result row.  Any pointer may be NULL.  DSP_E_STATE when the LAST run was not made with the posterior on (no run yet, or
+ * level 0: records of an earlier run are not handed out beside newer result rows), and for a non-NULL level-2 pointer when it was at level 1. */
+int dsp_batch_posterior_fetch(dsp_batch* b, int32_t* status, double* info_pose, double* cov_pose, double* var_code, float* loss, int64_t* M,
+                              int64_t* V, int64_t* K, double* Lambda, double* g, float* t_obj_cam, float* code, float* depths);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */
@@ -387,7 +425,8 @@ int dsp_batch_debug_start_state(dsp_batch* b, const float* t_obj_cam, const floa
 /* Forensics: iteration e < n_iterations of the following runs samples the rays at depths[(e * n_objects + i) * 64 ..] instead of
  * the depths derived from the pose (n_iterations = 0 turns the schedule off). */
 int dsp_batch_debug_depth_schedule(dsp_batch* b, const float* depths, int32_t n_iterations);
-/* Forensics: the per-sample arrays the LAST iteration of the last run left behind for object obj, expanded to
+/* Forensics: the per-sample arrays the LAST iteration of the last run left behind for object obj (with the posterior on, that is the
+ * posterior pass: it is then the last linearisation of the last run, at the returned state), expanded to
  * (n_rays x num_depth_samples) grids: raymask (n_rays; bit j = sample j lies inside the unit sphere), ssdf (the sdf the occupancy
  * scan read: fp32 inside the band, the prepass value or the placeholder 1.0 elsewhere; NaN = not in the sphere), sdeds (de_ds of a kept
  * sample, 0 = not kept, NaN = not in the sphere).  cap = floats available in ssdf / sdeds (>= n_rays * num_depth_samples). */

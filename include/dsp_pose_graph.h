@@ -47,6 +47,19 @@ int dsp_pg_edge_linearize(int64_t n, const double* meas, const double* err, doub
 int dsp_pg_edge_chi2(int64_t n, const double* err, double inv_sigma, double huber_delta, double* chi2_out, double* rho_out,
                      double* weight_out);
 
+/* Information of the 6-dof camera-object edge in g2o's [omega | upsilon] error coordinates, from the optimiser's pose information
+ * (dsp_batch_posterior_fetch: info_pose, n x dof x dof, unknowns [v(3), w(3), sigma]; dof 7 joint, 6 pose-only), in place of the constant
+ * 1e3 I.  The optimiser updates T_oc <- exp(delta) T_oc and the measurement is the rigid part [R / s | t] of T_co = T_oc^-1, so to first
+ * order meas' = meas exp_se3(-[s v, w]) and the edge error moves by [omega, upsilon] = [w, s v].  With dof 7 sigma is marginalised first
+ * (Schur complement S over index 6); then Omega_ww = S_ww, Omega_wu = S_wv / s, Omega_uu = S_vv / s^2, all times gain.  scale[i] = the
+ * object's scale: det(R_co)^(1/3) of the returned t_cam_obj (joint), the scale argument (pose-only).  Use the records of DSP_POSTERIOR_SUM.
+ * DSP_E_ARG: scale <= 0, a non-positive S_sigma_sigma, another dof.  info66_out: n x 6 x 6, row-major. */
+int dsp_pg_edge_information(int64_t n, int dof, const double* info_pose, const double* scale, double gain, double* info66_out);
+
+/* chi2 = err^T Omega err with a full information matrix (n x 6 x 6), then the Huber kernel exactly as dsp_pg_edge_chi2. */
+int dsp_pg_edge_chi2_info(int64_t n, const double* err, const double* info66, double huber_delta, double* chi2_out, double* rho_out,
+                          double* weight_out);
+
 /* Vertex update.  kind DSP_PG_VERTEX_EXPMAP: exp(update) * estimate (VertexSE3Expmap);  DSP_PG_VERTEX_OBJECT:
  * estimate * SE3Quat(update)^-1 where SE3Quat(update) is g2o's 6-vector constructor [t | q.xyz] (se3quat.h:70-84), as
  * VertexSE3Object::oplusImpl is written. */

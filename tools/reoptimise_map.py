@@ -22,6 +22,10 @@ as one dsp_batch on its own handle from its own host thread, and the result rows
 
 --tol POSE CODE (off without the flag) lets every object stop once its Gauss-Newton step is below the tolerances (dsp_batch_convergence).  The
 iterations each object used are printed: how many a warm start saves depends on the map (profiles/early_stop.md).
+
+--posterior FILE.npz writes, for every map object, the posterior record of the run (dsp_batch_posterior, "sum" weights: ids, status, info_pose,
+cov_pose, var_code, loss, M, V, K; objects without an observation have status 1 = none), and prints which objects are poorly constrained.
+The poses and codes written are bit for bit those of a run without the flag.
 """
 import argparse
 import os
@@ -79,12 +83,14 @@ def iterations_histogram(iters):
     return "mean %.2f over %d objects; %s" % (float(iters.mean()), iters.size, ", ".join("%d: %d" % (v, c) for v, c in zip(vals, cnt)))
 
 
-def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None):
+def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
     tol: None, or (pose_tol, code_tol[, min_iterations]): the per-object convergence rule; stats["iterations_used"] then holds the updates applied
-    to every observed object (None without tol)."""
+    to every observed object (None without tol).
+    posterior: None, "mean" or "sum": stats["posterior"] then holds Batch.posterior()'s level-1 arrays with one row per MAP object (status 1 =
+    none for objects without an observation)."""
     from dsp_slam_amd import distributed as D
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
@@ -98,6 +104,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                                  len(engines))
     parts = [None] * len(shards)
     used = [None] * len(shards)
+    post = [None] * len(shards)
     multiview = any("more_views" in obs[i] for i in idx)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
@@ -106,7 +113,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if tol is not None and b > a:      # the rule lives on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -114,10 +121,15 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
             try:
                 if compute != 0:
                     bt.set_compute(compute)
-                bt.set_convergence(*tol)
+                if tol is not None:
+                    bt.set_convergence(*tol)
+                if posterior is not None:
+                    bt.set_posterior(1, posterior)
                 bt.run()
                 parts[r] = D.pack_results(*bt.results())
                 used[r] = bt.iterations_used()
+                if posterior is not None:
+                    post[r] = bt.posterior()
             finally:
                 bt.close()
             return
@@ -147,8 +159,21 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         out[i]["code"] = codes[k, :len(objs[i]["code"])].astype(np.float32)
         out[i]["loss"] = float(loss[k])
     iters = None if tol is None else np.concatenate([u for u in used if u is not None] + [np.zeros(0, np.int32)])
+    records = None
+    if posterior is not None:
+        n = len(objs)
+        records = dict(ids=np.array([o["id"] for o in objs], np.int64), status=np.ones(n, np.int32), info_pose=np.zeros((n, 7, 7)), cov_pose=np.zeros((n, 7, 7)),
+                       var_code=np.zeros((n, code_len)), loss=np.zeros(n, np.float32), M=np.zeros(n, np.int64), V=np.zeros(n, np.int64), K=np.zeros(n, np.int64))
+        k = 0
+        for pr in post:
+            if pr is None:
+                continue
+            m = pr["status"].shape[0]
+            for key in ("status", "info_pose", "cov_pose", "var_code", "loss", "M", "V", "K"):
+                records[key][idx[k:k + m]] = pr[key]
+            k += m
     return out, dict(n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
-                     iterations_used=iters)
+                     iterations_used=iters, posterior=records)
 
 
 def main():
@@ -161,6 +186,8 @@ def main():
                     help="f32 = the parity path (default); f16 / bf16 = the opt-in low-precision compute mode: ~3.7 x the objects/s on large maps, accuracy in profiles/r06_lp_compute.md")
     ap.add_argument("--tol", type=float, nargs=2, metavar=("POSE", "CODE"), default=None,
                     help="stop each object once its Gauss-Newton step is below these tolerances (pose entries / code entries); off without the flag")
+    ap.add_argument("--posterior", default=None, metavar="FILE.npz",
+                    help="write every map object's posterior record (pose information / covariance, code variance, loss at the result) of this run")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -173,13 +200,21 @@ def main():
     decoders = [config_decoder(cfg.DeepSDF_DIR).cuda(d) for d in range(n_dev)]        # one decoder (= one handle, one stream) per GPU
     prm = E.params_from_configs(cfg)
     out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute],
-                         tol=None if args.tol is None else tuple(args.tol))
+                         tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum")
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
         st["n_good"], st["n_objects"], st["n_observed"], n_dev, st["seconds"], st["n_observed"] / max(st["seconds"], 1e-9), dst))
     if st["iterations_used"] is not None:
         print("iterations used: %s" % iterations_histogram(st["iterations_used"]))
+    if st["posterior"] is not None:
+        rec = st["posterior"]
+        np.savez(args.posterior, **rec)
+        ok = rec["status"] == 0
+        sd = np.sqrt(np.maximum(np.diagonal(rec["cov_pose"], axis1=1, axis2=2), 0.0))
+        worst = np.argsort(-sd[:, 3:6].max(1) * ok)[:min(5, int(ok.sum()))]
+        print("posterior records of %d objects (%d ok) -> %s; largest rotation standard deviations: %s" % (
+            rec["status"].shape[0], int(ok.sum()), args.posterior, ", ".join("id %d: %.3g rad" % (rec["ids"][i], sd[i, 3:6].max()) for i in worst)))
 
 
 if __name__ == "__main__":

@@ -99,6 +99,10 @@ SYMBOLS = [
     ("dsp_batch_iterations_used", C.c_int, [_VP, c_i32p]),
     ("dsp_batch_posterior", C.c_int, [_VP, C.c_int, C.c_int]),
     ("dsp_batch_posterior_fetch", C.c_int, [_VP, c_i32p, c_f64p, c_f64p, c_f64p, c_f32p, c_i64p, c_i64p, c_i64p, c_f64p, c_f64p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_batch_prior", C.c_int, [_VP, c_f32p, c_f32p, c_f64p]),
+    ("dsp_batch_prior_fetch", C.c_int, [_VP, c_f64p, c_f64p]),
+    ("dsp_debug_prior_check", C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f64p]),
+    ("dsp_debug_prior_terms", C.c_int, [C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p]),
     ("dsp_sdf_jacobian_lp", C.c_int, [_VP, C.c_int, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p]),
     ("dsp_batch_set_debug", C.c_int, [_VP, C.c_int, C.c_int]),
     ("dsp_prepass_calibration", C.c_int, [_VP, C.c_int, c_f32p, c_f32p]),

@@ -6,6 +6,8 @@
 #include <string.h>
 #include <stdexcept>
 
+#include "prior_math.h"
+
 namespace dsp {
 
 // ---- decoder geometry the MLP kernel is built for (DeepSDF as used by DSP-SLAM) -------------
@@ -282,6 +284,19 @@ struct StopRule {
     int min_iterations;
 };
 
+// Gaussian prior on pose and code (dsp_batch_prior; arithmetic in prior_math.h), per OBJECT (multi-view: per object, not per view):
+// k_prior_terms reads the state, t0, z0 and Lp and leaves [H_extra | b_extra] in `extra` for k_solve<.., PRIOR = true> / k_posterior<., true>;
+// its final pass leaves e and chi2 in `res` (prior_math::RES_STRIDE doubles per object) for the run's read-back.
+struct PriorDev {
+    const float* t0 = nullptr;          // 16 per object: the prior's t_obj_cam
+    const float* z0 = nullptr;          // CODE_LEN per object
+    const double* Lp = nullptr;         // n x n per object, symmetric bit for bit
+    const unsigned char* on = nullptr;  // per object: 0 = Lambda is all zero, the object has no prior
+    double* extra = nullptr;            // n x (n + 1) per object
+    double* res = nullptr;
+    int n = 0;                          // 71, pose-only batches 6
+};
+
 // kernels_mlp / kernels_gn launchers
 size_t mlp_lds_bytes(int mode);
 void launch_code_bias(const float* codew, const float* b0, const float* blat, const float* codes, int code_stride, float* out, int n_obj, hipStream_t s);
@@ -350,7 +365,7 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 // leader (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
-                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr);    // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr, const PriorDev* prior = nullptr);    // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
 // the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
 // -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
@@ -362,7 +377,10 @@ constexpr int POSTERIOR_REC_L1 = 168;
 constexpr int POSTERIOR_REC_L2 = POSTERIOR_REC_L1 + 71 * 71 + 71 + (16 + CODE_LEN + MAX_DEPTH_SAMPLES) / 2;
 void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
-                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr);
+                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr,
+                      const PriorDev* prior = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
+// the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass: e and chi2 at the returned state
+void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
 void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,
                      const GroupEnt* grp = nullptr, unsigned* iters_out = nullptr /*optional B: ObjState::n_iter*/);   // grp: one row per OBJECT, written by the group's leader

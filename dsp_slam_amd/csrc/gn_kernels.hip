@@ -1330,6 +1330,60 @@ __global__ __launch_bounds__(64) void k_group_broadcast(const GroupEnt* grp, Obj
     }
 }
 
+// Gaussian prior on pose and code (dsp_batch_prior; the arithmetic: prior_math.h).  One workgroup per object (multi-view: the group's leader),
+// in front of k_solve: e = [Log(T_oc T0^-1) | z - z0], J = blkdiag(J_p, I), and the block [J^T Lp J | -J^T Lp e] (n x (n + 1) doubles, fp64, every sum
+// in a fixed order, no atomics) that k_solve<.., PRIOR = true> adds to its system.  An object without a prior (Lambda all zero) or not GOOD
+// is left alone.  A rotation of T_oc T0^-1 beyond pi - 1e-3 (or a state whose linear part has no positive determinant) ends the object
+// DSP_STATUS_NAN: a prior half a turn away from the state contradicts it.
+// final_pass: the record of the run's read-back instead -- e (P + 64 doubles) and chi2 = e^T Lp e at the RETURNED state; NaN for an object
+// that did not end good; nothing k_finalize reads is written (no status word either).
+constexpr int PRIOR_THREADS = 256;
+__global__ __launch_bounds__(PRIOR_THREADS) void k_prior_terms(ObjState* st, GnParamsDev prm, PriorDev pr, const GroupEnt* grp, int final_pass) {
+    __shared__ prior_math::Work w;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int ob = b;
+    if (grp) {
+        const GroupEnt g = grp[b];
+        if (g.leader != b) return;
+        ob = g.object;
+    }
+    ObjState& s = st[b];
+    const int status = s.status;
+    const bool on = pr.on[ob] != 0;
+    const int P = prm.pose_only ? 6 : 7, n = pr.n, live = prm.pose_only ? 6 : 7 + prm.code_len;
+    double* res = pr.res + (size_t)ob * prior_math::RES_STRIDE;
+    if (final_pass) {
+        if (status == DSP_STATUS_SKIP) return;        // partial re-run: the record of the earlier run stands, like the result row
+        if (status != DSP_STATUS_GOOD && status != DSP_STATUS_DONE) {
+            for (int i = tid; i < prior_math::RES_STRIDE; i += PRIOR_THREADS) res[i] = nan("");
+            return;
+        }
+        if (!on) {
+            for (int i = tid; i < prior_math::RES_STRIDE; i += PRIOR_THREADS) res[i] = 0.0;
+            return;
+        }
+    } else if (status != DSP_STATUS_GOOD || !on) {
+        return;
+    }
+    const double* Lp = pr.Lp + (size_t)ob * n * n;
+    prior_math::phase0(w, tid, PRIOR_THREADS, P, prm.pose_only != 0, s.t_oc, s.code, pr.t0 + 16 * (size_t)ob, pr.z0 + CODE_LEN * (size_t)ob);
+    __syncthreads();
+    if (!w.ok) {                                      // uniform
+        if (final_pass) { for (int i = tid; i < prior_math::RES_STRIDE; i += PRIOR_THREADS) res[i] = nan(""); }
+        else if (tid == 0) s.status = DSP_STATUS_NAN;
+        return;
+    }
+    prior_math::phase1(w, tid, PRIOR_THREADS, P, n, Lp);
+    __syncthreads();
+    if (final_pass) {
+        for (int i = tid; i < prior_math::RES_STRIDE - 1; i += PRIOR_THREADS) res[i] = i < n ? w.e[i] : 0.0;
+        if (tid == 0) res[prior_math::RES_STRIDE - 1] = prior_math::chi2_of(w, n);
+        return;
+    }
+    double* ex = pr.extra + (size_t)ob * n * (n + 1);
+    for (int idx = tid; idx < n * (n + 1); idx += PRIOR_THREADS) ex[idx] = prior_math::extra_entry(w, idx / (n + 1), idx % (n + 1), P, n, live, Lp);
+}
+
 constexpr int SOLVE_THREADS = 1024;   // 16 waves: assembly, trace and the code bias use all of them; the elimination nine
 constexpr int NS1 = NSOLVE + 1;       // rows of the augmented system: the unknowns + the right-hand side as row n
 
@@ -1352,11 +1406,15 @@ template <bool V> struct BoolC { static constexpr bool value = V; };
 // STOP (dsp_batch_convergence): the convergence rule (StopRule) is evaluated on the step this launch applies, and an object that meets it
 // is frozen: status DSP_STATUS_DONE, which every kernel of the run's remaining launches treats like a failed object (no work, no writes)
 // and k_finalize reports as good.  STOP = false is the code of every run without a rule -- a template argument like GROUPS, for the same reason.
-template <bool GROUPS, bool STOP>
+// PRIOR (dsp_batch_prior): the block [H_extra | b_extra] k_prior_terms has left for the object is added to the system -- to H behind the k4
+// term and in FRONT of the damping, so that H is (Lambda + damping) with the Lambda k_posterior<., true> reports, bit for bit; to b as the
+// last addition.  Entries of rows or columns beyond the decoder's code length are not added.  PRIOR = false is the code of every run without
+// a prior: a template argument like the other two.
+template <bool GROUPS, bool STOP, bool PRIOR>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int iter,
                                                          const float* codew, const float* cb0, const float* cblat, float* cbias,
                                                float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj,
-                                               const GroupEnt* grp, const int* gmk, StopRule stop) {
+                                               const GroupEnt* grp, const int* gmk, StopRule stop, PriorDev pr) {
     __shared__ double A[NS1][NS1 + 1];          // [H | b] in rows 0..n-1 (b = column n); b is also kept as ROW n (rows 64 .. 71 are one register of the elimination)
     const int b = blockIdx.x, tid = threadIdx.x;
     if constexpr (GROUPS) { if (grp[b].leader != b) return; }
@@ -1389,6 +1447,15 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     constexpr int RG = 12, RPT = (NSOLVE + RG - 1) / RG;
     double g0[RPT], g1[RPT];
     float zq[RPT];
+    [[maybe_unused]] double ex[RPT];
+    [[maybe_unused]] bool pr_on = false;
+    [[maybe_unused]] const double* exb = nullptr;
+    if constexpr (PRIOR) {
+        int ob = b;
+        if constexpr (GROUPS) ob = grp[b].object;
+        pr_on = pr.on[ob] != 0;
+        exb = pr.extra + (size_t)ob * pr.n * (pr.n + 1);
+    }
     if (!prm.pose_only) {
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
@@ -1398,6 +1465,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
             const int gi = live ? i * 72 + col : 0;
             g0[q] = gram(0, gi);
             g1[q] = gram(1, gi);
+            if constexpr (PRIOR) ex[q] = exb[gi];        // the prior's block has the same 72-column rows (column 71 = b_extra)
             zq[q] = s.code[min(max(i - pd, 0), CODE_LEN - 1)];             // the right-hand side's k3 z term (optimizer.py:172); unconditional: a
                                                                            // load in a branch is waited for at the branch's end
         }
@@ -1431,6 +1499,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
                 // k3 on the diagonal and 0 on the right -- pinned to the identity so that they stay decoupled (dx = 0) even with k3 = 0
                 if (i >= pd + prm.code_len && i == j) v = 1.0;
                 if (i < pd && j < pd) v += (double)prm.k4 * (double)jr(i) * (double)jr(j);       // :176,178
+                if constexpr (PRIOR) { if (pr_on && i < pd + prm.code_len && j < pd + prm.code_len) v += ex[q]; }     // J^T Lp J
                 if (i < pd && i == j) v += 1.0;                                                // :183
                 if (i == pd - 1 && j == pd - 1) v += (double)prm.s_damp;                       // :184
             } else {
@@ -1438,6 +1507,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
                 if (i >= pd) v -= (double)prm.k3 * (double)zq[q];                              // :172
                 if (i >= pd + prm.code_len) v = 0.0;
                 if (i < pd) v += (double)prm.k4 * (double)jr(i) * (double)res_rot;             // :177,179 (sign as written)
+                if constexpr (PRIOR) { if (pr_on && i < pd + prm.code_len) v += ex[q]; }         // -J^T Lp e
             }
             A[i][j] = v;
         }
@@ -1454,8 +1524,14 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         for (int e = tid; e < n * (n + 1); e += SOLVE_THREADS) {
             const int i = e / (n + 1), j = e % (n + 1);
             double v;
-            if (j < n) { v = gram(0, i * 72 + j) / (double)Ma; if (i == j) v += 1e-2; }
-            else v = -gram(0, i * 72 + 71) / (double)Ma;
+            if (j < n) {
+                v = gram(0, i * 72 + j) / (double)Ma;
+                if constexpr (PRIOR) { if (pr_on) v += exb[e]; }
+                if (i == j) v += 1e-2;
+            } else {
+                v = -gram(0, i * 72 + 71) / (double)Ma;
+                if constexpr (PRIOR) { if (pr_on) v += exb[e]; }
+            }
             A[i][j] = v;
         }
     }
@@ -1728,9 +1804,10 @@ __global__ void k_posterior_park(ObjState* st, int* park, int n_obj) {
 constexpr int POST_L1 = POSTERIOR_REC_L1;
 static_assert(POSTERIOR_REC_L2 == POST_L1 + NSOLVE * NSOLVE + NSOLVE + (16 + CODE_LEN + MAX_DEPTH_SAMPLES) / 2, "posterior record layout");
 constexpr int POST_THREADS = 1024;
-template <bool GROUPS>
+// PRIOR (dsp_batch_prior): Lambda and g include the prior's block, added where k_solve<.., true> adds it.
+template <bool GROUPS, bool PRIOR>
 __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int weights, int level,
-                                                            const int* park, const GroupEnt* grp, const int* gmk, double* rec, int rec_stride) {
+                                                            const int* park, const GroupEnt* grp, const int* gmk, double* rec, int rec_stride, PriorDev pr) {
     __shared__ double A[NSOLVE][NSOLVE + 1];
     __shared__ double s_c[NSOLVE + 1], s_d0[NSOLVE + 1];
     __shared__ int s_sing;
@@ -1800,17 +1877,27 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
         w_r = weights ? (double)prm.k1 : (double)prm.k1 / (double)K;
     }
     auto jr = [=](int i) { return i == 3 ? jrot3 : (i == 5 ? jrot5 : 0.f); };
+    [[maybe_unused]] bool pr_on = false;
+    [[maybe_unused]] const double* exb = nullptr;
+    [[maybe_unused]] int xs = 0;             // row length of the prior's block; its last column is b_extra
+    if constexpr (PRIOR) {
+        pr_on = pr.on[row_i] != 0;
+        xs = pr.n + 1;
+        exb = pr.extra + (size_t)row_i * pr.n * xs;
+    }
     // entry (i, j), i >= j, of Lambda from the Gram sums (also re-read by the refinement of cov_pose below: the sweeps overwrite A)
     auto lam = [&](int i, int j) -> double {
         if (prm.pose_only) {
             double v = G0p[i * 72 + j];
             if (!weights) v = v / (double)M;
+            if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + j]; }
             return v;
         }
         const double g0 = G0p[i * 72 + j], g1 = G1p[i * 72 + j];
         double v = w_s * g0 + w_r * g1;
         if (i >= pd && i == j) v += (double)prm.k3;
         if (i < pd && j < pd) v += (double)prm.k4 * (double)jr(i) * (double)jr(j);
+        if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + j]; }
         return v;
     };
     if (!prm.pose_only) {
@@ -1826,6 +1913,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
                 double v = -(w_s * g0 + w_r * g1);
                 if (i >= pd) v -= (double)prm.k3 * (double)s.code[i - pd];
                 if (i < pd) v += (double)prm.k4 * (double)jr(i) * (double)res_rot;
+                if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + xs - 1]; }
                 s_c[i] = v;
             }
         }
@@ -1840,6 +1928,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
             } else {
                 double v = -G0p[i * 72 + 71];
                 if (!weights) v = v / (double)M;
+                if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + xs - 1]; }
                 s_c[i] = v;
             }
         }
@@ -2090,36 +2179,45 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 }
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
-                  const GroupEnt* grp, int* gmk, const StopRule* stop) {
+                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior) {
     const StopRule rule = stop ? *stop : StopRule{0.0, 0.0, 1};
+    const PriorDev pr = prior ? *prior : PriorDev{};
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
     if (!grp) {
-        auto k = stop ? k_solve<false, true> : k_solve<false, false>;
+        if (prior) launch_prior_terms(st, prm, pr, nullptr, 0, B, s);
+        auto k = prior ? (stop ? k_solve<false, true, true> : k_solve<false, false, true>) : (stop ? k_solve<false, true, false> : k_solve<false, false, false>);
         hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rule);
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr);
         return;
     }
     hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B);
-    auto k = stop ? k_solve<true, true> : k_solve<true, false>;
+    if (prior) launch_prior_terms(st, prm, pr, grp, 0, B, s);
+    auto k = prior ? (stop ? k_solve<true, true, true> : k_solve<true, false, true>) : (stop ? k_solve<true, true, false> : k_solve<true, false, false>);
     hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
-                       (const int*)gmk, rule);
+                       (const int*)gmk, rule, pr);
     launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
+}
+void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_prior_terms, dim3(B), dim3(PRIOR_THREADS), 0, s, st, prm, pr, grp, final_pass);
 }
 void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_posterior_park, dim3((B + 63) / 64), dim3(64), 0, s, st, park, B);
 }
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
-                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk) {
+                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk, const PriorDev* prior) {
     // the reductions launch_solve runs (no trace row), then the record
+    const PriorDev pr = prior ? *prior : PriorDev{};
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
     if (!grp) {
-        hipLaunchKernelGGL(k_posterior<false>, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride);
+        auto k = prior ? k_posterior<false, true> : k_posterior<false, false>;
+        hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park,
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride, pr);
         return;
     }
     hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, 0, (float*)nullptr, B);
-    hipLaunchKernelGGL(k_posterior<true>, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park, grp,
-                       (const int*)gmk, rec, rec_stride);
+    auto k = prior ? k_posterior<true, true> : k_posterior<true, false>;
+    hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park, grp,
+                       (const int*)gmk, rec, rec_stride, pr);
 }
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_group_broadcast, dim3(B), dim3(64), 0, s, grp, st, cbias, depths, n_depth);

@@ -155,6 +155,35 @@ class Batch(object):
         out["var_code"] = np.ascontiguousarray(out["var_code"][:, :self.engine.code_len])
         return out
 
+    # ---- Gaussian prior on pose and code (dsp_batch_prior, include/dsp_gn.h): fuse an earlier estimate into the run -------------------------
+    def set_prior(self, t_obj_cam0=None, code0=None, Lambda=None):
+        """Per object: t_obj_cam0 (4, 4) camera -> object, code0 (code_len or 64; ignored by pose-only batches), Lambda (71, 71) float64
+        (pose-only: (6, 6)) in the order [v, w, sigma | code] -- the t_obj_cam, code and Lambda of a level-2 Batch.posterior() can be passed as
+        they are (mind that such a Lambda already contains the k3 and k4 terms).  An object whose Lambda is all zero has no prior.  All None =
+        off, the initial state."""
+        lib, h = L.load(), self.engine._h
+        if t_obj_cam0 is None and code0 is None and Lambda is None:
+            L.check(lib.dsp_batch_prior(self._h, None, None, None), h, "dsp_batch_prior")
+            return
+        n, N = self.n, 6 if self.pose_only else 71
+        if t_obj_cam0 is None or Lambda is None or (code0 is None and not self.pose_only):
+            raise ValueError("set_prior takes t_obj_cam0, code0 and Lambda together (code0 may be None for pose-only batches), or all None")
+        t = L.f32(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in t_obj_cam0]))
+        lam = np.ascontiguousarray(np.stack([_prior_lambda(x, N) for x in Lambda]))
+        c = None if self.pose_only or code0 is None else L.f32(np.stack([L.code64(x) for x in code0]))
+        if t.shape[0] != n or lam.shape[0] != n or (c is not None and c.shape[0] != n):
+            raise ValueError("set_prior: one t_obj_cam0, code0 and Lambda per object (%d)" % n)
+        L.check(lib.dsp_batch_prior(self._h, L.ptr(t), L.ptr(c), L.ptr(lam, L.c_f64p)), h, "dsp_batch_prior")
+
+    def prior_residual(self):
+        """dict(e float64 (n, P + code_len) = [Log(T_oc T0^-1) | z - z0] (pose-only: (n, 6)), chi2 float64 (n,) = e^T Lambda e) at the state
+        the last run RETURNED (dsp_batch_prior_fetch): NaN for an object that did not end good, 0 for an object without a prior."""
+        n, P = self.n, 6 if self.pose_only else 7
+        e = np.zeros((n, P + L.CODE_LEN))
+        chi2 = np.zeros(n)
+        L.check(L.load().dsp_batch_prior_fetch(self._h, L.ptr(e, L.c_f64p), L.ptr(chi2, L.c_f64p)), self.engine._h, "dsp_batch_prior_fetch")
+        return dict(e=np.ascontiguousarray(e[:, :P] if self.pose_only else e[:, :P + self.engine.code_len]), chi2=chi2)
+
     # ---- testing: pin one of the bit-identical forms the library chooses between by itself (dsp_batch_set_debug) --------------------------
     def set_debug(self, key, value):
         L.check(L.load().dsp_batch_set_debug(self._h, int(key), int(value)), self.engine._h, "dsp_batch_set_debug(%d, %d)" % (key, value))
@@ -311,6 +340,35 @@ def _posterior_args(posterior):
     if isinstance(posterior, (tuple, list)):
         return int(posterior[0]), posterior[1]
     return 1, posterior
+
+
+def _run_resident(b, convergence, posterior, prior):
+    """The optional rules of the Engine's one-call forms on a resident batch: -> results() [+ (posterior(),)] [+ (prior_residual(),)]."""
+    if convergence is not None:
+        b.set_convergence(*convergence)
+    if posterior is not None:
+        b.set_posterior(*_posterior_args(posterior))
+    if prior is not None:
+        b.set_prior(*_prior_args(prior))
+    b.run()
+    return b.results() + (() if posterior is None else (b.posterior(),)) + (() if prior is None else (b.prior_residual(),))
+
+
+def _prior_lambda(lam, n):
+    """One object's Lambda as (n, n) float64; a pose-only batch (n = 6) also takes the (71, 71) a level-2 posterior record holds: its 6 x 6 block."""
+    lam = np.asarray(lam, np.float64)
+    if n == 6 and lam.shape == (71, 71):
+        lam = lam[:6, :6]
+    return lam.reshape(n, n)
+
+
+def _prior_args(prior):
+    """prior= of the Engine calls: dict(t_obj_cam, code, Lambda) of per-object arrays (a level-2 Batch.posterior() as it is) or a
+    (t_obj_cam0, code0, Lambda) tuple -> the arguments of Batch.set_prior."""
+    if isinstance(prior, dict):
+        return prior["t_obj_cam"], prior.get("code"), prior["Lambda"]
+    t0, c0, lam = prior
+    return t0, c0, lam
 
 
 def _flatten_views(views_per_object):
@@ -661,24 +719,21 @@ class Engine(object):
         set_start_state(t_obj_cam) work on it; results()[0] is estimate_pose_batch's output, bit for bit."""
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
-    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, posterior=None):
+    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, posterior=None, prior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
         convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
         posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
-        (the first four are bit for bit those of the call without it)."""
+        (the first four are bit for bit those of the call without it).
+        prior: None, or dict(t_obj_cam, code, Lambda) / (t_obj_cam0, code0, Lambda) of per-object arrays -- Batch.set_prior; the call then
+        returns Batch.prior_residual() as its LAST item (behind the posterior, where both are asked for)."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
-            return empty if posterior is None else empty + ({},)
+            return empty + (() if posterior is None else ({},)) + (() if prior is None else ({},))
         b = Batch(self, prm, t_cam_obj, pts, rays, depth, codes)
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
-            if convergence is not None:
-                b.set_convergence(*convergence)
-            if posterior is not None:
-                b.set_posterior(*_posterior_args(posterior))
-            b.run()
-            return b.results() if posterior is None else b.results() + (b.posterior(),)
+            return _run_resident(b, convergence, posterior, prior)
         finally:
             b.close()
 
@@ -686,23 +741,18 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None):
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, prior=None):
         """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
         convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call.
-        posterior: as reconstruct_batch (a resident batch too; a fifth item, per object)."""
+        posterior, prior: as reconstruct_batch (a resident batch too; further items, per object)."""
         n = len(views)
         if n == 0:
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
-            return empty if posterior is None else empty + ({},)
-        if convergence is not None or posterior is not None:
+            return empty + (() if posterior is None else ({},)) + (() if prior is None else ({},))
+        if convergence is not None or posterior is not None or prior is not None:
             b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
             try:
-                if convergence is not None:
-                    b.set_convergence(*convergence)
-                if posterior is not None:
-                    b.set_posterior(*_posterior_args(posterior))
-                b.run()
-                return b.results() if posterior is None else b.results() + (b.posterior(),)
+                return _run_resident(b, convergence, posterior, prior)
             finally:
                 b.close()
         vo, t_ref, pts, rays, depth = _flatten_views(views)
@@ -718,21 +768,19 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, prior=None):
         """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
-        one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior())."""
+        one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior()).
+        prior: as reconstruct_batch, with (6, 6) Lambdas and t_obj_cam0 carrying the scale; Batch.prior_residual() is then the last item."""
         n = len(pts)
         if n == 0:
-            return np.zeros((0, 4, 4), np.float32) if posterior is None else (np.zeros((0, 4, 4), np.float32), {})
-        if convergence is not None or posterior is not None:
+            extra = (() if posterior is None else ({},)) + (() if prior is None else ({},))
+            return np.zeros((0, 4, 4), np.float32) if not extra else (np.zeros((0, 4, 4), np.float32),) + extra
+        if convergence is not None or posterior is not None or prior is not None:
             b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
             try:
-                if convergence is not None:
-                    b.set_convergence(*convergence)
-                if posterior is not None:
-                    b.set_posterior(*_posterior_args(posterior))
-                b.run()
-                return b.results()[0] if posterior is None else (b.results()[0], b.posterior())
+                res = _run_resident(b, convergence, posterior, prior)
+                return res[0] if len(res) == 4 else (res[0],) + res[4:]
             finally:
                 b.close()
         po, p = _ragged(pts, 3)

@@ -92,25 +92,51 @@ class Optimizer(object):
                                  self.num_iterations_pose_only)
 
     # ---- pose only (reference optimizer.py:45-86) ---------------------------------------------------
-    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes, return_posterior=False):
+    @staticmethod
+    def _stack_priors(priors, n_unknowns, code_len):
+        """[dict(t_obj_cam, code, Lambda) or None per object] -> the per-object arrays Engine's prior= takes; None = no prior (Lambda 0)."""
+        t0 = np.tile(np.eye(4, dtype=np.float32), (len(priors), 1, 1))
+        z0 = np.zeros((len(priors), 64), np.float32)
+        lam = np.zeros((len(priors), n_unknowns, n_unknowns))
+        for i, p in enumerate(priors):
+            if p is None:
+                continue
+            t0[i] = _f32(p["t_obj_cam"]).reshape(4, 4)
+            if n_unknowns > 6:
+                c = _f32(p["code"]).reshape(-1)[:code_len]
+                z0[i, :c.shape[0]] = c
+            lam[i] = _engine._prior_lambda(p["Lambda"], n_unknowns)
+        return dict(t_obj_cam=t0, code=z0, Lambda=lam)
+
+    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes, return_posterior=False, priors=None):
         """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses.  return_posterior=True: (poses,
-        Batch.posterior() dict) -- 6 x 6 pose information / covariance per object, with the weights of pose_only_optim.posterior ("mean" if absent)."""
+        Batch.posterior() dict) -- 6 x 6 pose information / covariance per object, with the weights of pose_only_optim.posterior ("mean" if absent).
+        priors: None, or one dict(t_obj_cam (4, 4) with the scale in it, Lambda (6, 6)) or None per object (dsp_batch_prior); the call then
+        returns Batch.prior_residual() as its last item."""
         kw = {} if self.convergence_pose_only is None else {"convergence": self.convergence_pose_only}
         if return_posterior:
             kw["posterior"] = self.posterior_pose_only or "mean"
+        if priors is not None:
+            kw["prior"] = self._stack_priors(priors, 6, self.code_len)
         return self.decoder.engine.estimate_pose_batch(self._params(), [_f32(t) for t in t_co_se3_list], scales,
                                                        [_f32(p) for p in pts_list], [_f32(c) for c in codes], **kw)
 
-    def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code):
+    def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code, prior=None):
         """Pose-only refinement of one detection (reference optimizer.py:45-86; called from LocalMapping_util.cc:109-110).
         t_co_se3: (4, 4) rigid object-to-camera guess; scale: the object's scale (float); pts: (M, 3) surface points in the camera frame;
-        code: the object's shape code.  Returns the refined rigid object-to-camera matrix as a (4, 4) CPU torch.Tensor, like the reference."""
-        out = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code])
-        return torch.from_numpy(out[0].copy())
+        code: the object's shape code.  Returns the refined rigid object-to-camera matrix as a (4, 4) CPU torch.Tensor, like the reference.
+        prior (an addition): dict(t_obj_cam, Lambda (6, 6)) -- the last estimate of this object and its information (one row of a pose-only
+        Batch.posterior() at level 2); the call then returns a dict: t_cam_obj (the tensor), prior_chi2, prior_residual (6,)."""
+        if prior is None:
+            out = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code])
+            return torch.from_numpy(out[0].copy())
+        out, res = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], priors=[prior])
+        return ForceKeyErrorDict(t_cam_obj=torch.from_numpy(out[0].copy()), prior_chi2=float(res["chi2"][0]), prior_residual=res["e"][0].copy())
 
     # ---- joint shape + pose (reference optimizer.py:88-203) -----------------------------------------
-    def reconstruct_objects(self, t_cam_obj_list, pts_list, rays_list, depth_list, codes=None):
-        """Batched form: B independent objects in one device run -> list of result dicts."""
+    def reconstruct_objects(self, t_cam_obj_list, pts_list, rays_list, depth_list, codes=None, priors=None):
+        """Batched form: B independent objects in one device run -> list of result dicts.  priors: None, or one dict(t_obj_cam, code,
+        Lambda (71, 71)) or None per object (dsp_batch_prior); good objects then carry prior_chi2 and prior_residual."""
         B = len(pts_list)
         codes_in = None
         if codes is not None:
@@ -118,6 +144,8 @@ class Optimizer(object):
         kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
         if self.posterior_joint is not None:
             kw["posterior"] = self.posterior_joint
+        if priors is not None:
+            kw["prior"] = self._stack_priors(priors, 71, self.code_len)
         res = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
             [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)
@@ -126,7 +154,7 @@ class Optimizer(object):
         for i in range(B):
             if status[i] == _L.OBJ_GOOD:
                 out.append(ForceKeyErrorDict(t_cam_obj=t[i].copy(), code=code[i].copy(), is_good=True,
-                                             loss=torch.tensor(float(loss[i])), **self._posterior_fields(res, i)))
+                                             loss=torch.tensor(float(loss[i])), **self._posterior_fields(res, i), **self._prior_fields(res, i, priors)))
             else:   # reference: t_cam_obj=None, code=None, is_good=False, loss=<last computed loss> (:131,136,143,150)
                 out.append(ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[i])))
         return out
@@ -140,35 +168,46 @@ class Optimizer(object):
                     code_variance=post["var_code"][i].copy(), loss_at_result=float(post["loss"][i]),
                     posterior_ok=bool(post["status"][i] == _L.POSTERIOR_OK))
 
-    def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None):
+    @staticmethod
+    def _prior_fields(res, i, priors):
+        """The extra result fields of a good object of a call with priors (none otherwise): Batch.prior_residual() is the call's last item."""
+        if priors is None:
+            return {}
+        return dict(prior_chi2=float(res[-1]["chi2"][i]), prior_residual=res[-1]["e"][i].copy())
+
+    def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None, prior=None):
         """Joint shape + pose optimisation of one object (reference optimizer.py:88-203; LocalMapping_util.cc:179-180,391-392,402-403).
         t_cam_obj: (4, 4) Sim(3) object-to-camera start; pts: (M, 3) surface points in the camera frame; rays: (R, 3) ray directions, the
         first len(depth) of them foreground; depth: observed depth of the foreground rays (KITTI: one per surface point); code: optional
         start code (zeros when None).  Returns the reference's result dict: t_cam_obj, code, is_good, loss -- attribute access, KeyError on
-        anything else."""
+        anything else.  prior (an addition): dict(t_obj_cam, code, Lambda (71, 71)) -- one row of a level-2 Batch.posterior() can be passed
+        as it is -- fuses that earlier estimate into the run (dsp_batch_prior); the result then also has prior_chi2 and prior_residual."""
         start = get_time()
-        rst = self.reconstruct_objects([t_cam_obj], [pts], [rays], [depth], None if code is None else [code])[0]
+        rst = self.reconstruct_objects([t_cam_obj], [pts], [rays], [depth], None if code is None else [code], None if prior is None else [prior])[0]
         if self.verbose and rst.is_good:
             print("Reconstruction takes %f seconds" % (get_time() - start))
         return rst
 
-    def reconstruct_object_multiview(self, t_cam_obj, views, code=None):
+    def reconstruct_object_multiview(self, t_cam_obj, views, code=None, prior=None):
         """Joint shape + pose optimisation of one object from SEVERAL observations (an addition: the reference's reconstruct_object,
         optimizer.py:88-203, takes one, although its map keeps one per key frame).  t_cam_obj: (4, 4) Sim(3) object-to-camera start in the
         frame of the REFERENCE camera = the camera of views[0]; views: [dict(t_ref_cam, pts, rays, depth), ...] -- t_ref_cam (4, 4) rigid,
         that view's camera -> the reference camera (identity for views[0]); pts / rays / depth as reconstruct_object takes them, in that
         view's camera frame.  All views share one pose and one code; their rows are pooled into one Gauss-Newton system per iteration.
-        Same result dict as reconstruct_object; one view gives reconstruct_object's result, bit for bit."""
+        Same result dict as reconstruct_object; one view gives reconstruct_object's result, bit for bit.  prior: as reconstruct_object."""
         vs = [dict(t_ref_cam=_f32(v["t_ref_cam"]), pts=_f32(v["pts"]), rays=_f32(v["rays"]), depth=_f32(v["depth"]).reshape(-1)) for v in views]
         codes_in = None if code is None else [_f32(code)[:self.code_len]]
         kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
         if self.posterior_joint is not None:
             kw["posterior"] = self.posterior_joint
+        priors = None if prior is None else [prior]
+        if priors is not None:
+            kw["prior"] = self._stack_priors(priors, 71, self.code_len)
         res = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
         t, z, loss, status = res[:4]
         if status[0] == _L.OBJ_GOOD:
             return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])),
-                                     **self._posterior_fields(res, 0))
+                                     **self._posterior_fields(res, 0), **self._prior_fields(res, 0, priors))
         return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[0]))
 
     @staticmethod

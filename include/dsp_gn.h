@@ -396,6 +396,52 @@ int dsp_batch_posterior(dsp_batch* b, int level /* 0 off (initial), 1, 2 */, int
 int dsp_batch_posterior_fetch(dsp_batch* b, int32_t* status, double* info_pose, double* cov_pose, double* var_code, float* loss, int64_t* M,
                               int64_t* V, int64_t* K, double* Lambda, double* g, float* t_obj_cam, float* code, float* depths);
 
+/* ---- Gaussian prior on pose and code (optional): fuse an earlier estimate into a run -------------------------------------------------------
+ * Information form.  Unknowns are ordered as in H: [v(3), w(3), sigma | code(64)]; P = 7 for joint and multi-view batches, P = 6 (no code
+ * block) for pose-only batches.  Per OBJECT (multi-view: per object, not per view) the caller gives
+ *     t_obj_cam0  T0, 4 x 4 camera -> object -- the posterior record's t_obj_cam field (a pose-only batch: with the scale in it, as
+ *                 dsp_batch_debug_start_state takes it).  Both T0 and the state are read as affine maps: bottom rows taken as [0 0 0 1]
+ *     code0       z0, 64 floats (ignored, may be NULL, for pose-only batches)
+ *     Lambda      Lp, n x n float64, row-major, symmetric bit for bit; n = 71 (slots beyond the decoder's code length all zero), pose-only n = 6
+ * At the state (T_oc, z) of an iteration the prior's residual is
+ *     e_p = Log(T_oc T0^-1)    in fp64 from the two fp32 matrices: the logarithm of the STANDARD Sim(3) exponential,
+ *                              hat(xi) = [[w^ + sigma I, v], [0, 0]], translation solved from V v = t with V = int_0^1 exp(a (sigma I + w^)) da.
+ *                              NOT the inverse of the reference's exp_sim3 (loss_utils.py:188-233), whose `c = 0. if s <= eps` quirk has none.
+ *                              Closed forms for theta >= 1/4, series in theta^2 and sigma below (csrc/prior_math.h).  Pose-only: the same
+ *                              logarithm with the sigma entry dropped (both matrices carry the same scale).
+ *     e_c = z - z0
+ * linearised for the update T_oc <- exp(dx) T_oc by the BCH series of the inverse left jacobian,
+ *     J_p = I - 1/2 ad(e_p) + 1/12 ad(e_p)^2,   ad([v, w, s]) = [[w^ + s I, v^, -v], [0, w^, 0], [0, 0, 0]]   (pose-only: top-left 6 x 6, s = 0)
+ *     J   = blkdiag(J_p, I_code)
+ * -- signs confirmed by finite differences of Log(Exp(d) Exp(e)) in fp64 (tests/test_prior_host.py); the truncation error is fourth order in
+ * |e|.  Every iteration adds, in fp64 and in a fixed summation order, before the solve
+ *     H += J^T Lp J        behind the k4 term and in FRONT of the damping, so that H = Lambda + damping with the Lambda the posterior reports
+ *     b -= J^T Lp e        as the last addition
+ * Damping, k3 and k4 are unchanged.  WARNING: a posterior record (dsp_batch_posterior, level 2) already CONTAINS k3 I_code and the k4 rotation
+ * term; feeding it back as Lambda while the batch keeps k3 and k4 counts both twice -- subtract them, or run with k3 = k4 = 0.
+ * Entries with a row or column beyond P + the decoder's code length are never added (the pinned rows of 32-D codes stay as they are).  An object
+ * whose Lambda is all zero has NO prior: it returns the bits of a batch without one, as do its neighbours.  An object whose T_oc T0^-1 has a
+ * rotation angle beyond pi - 1e-3 ends DSP_OBJ_NAN: a prior half a turn from the state is a contradiction, not an estimate (the mono flip
+ * hypothesis is exactly this case).  The loss of the result row stays k1 L_render + k2 L_sdf.  With the posterior on, Lambda and g of the
+ * record include the prior's terms (the relation to a traced H and b holds with the same prior set); a frozen object (dsp_batch_convergence)
+ * gets no further prior terms; the partial re-run after a prepass-guard trip keeps the prior; every launch form and the low-precision
+ * compute mode take it.  All NULL = off, the initial state: such a run launches exactly the kernels of a batch that never had a prior.
+ * DSP_E_ARG (the previous setting stays): some but not all pointers NULL, a non-finite input, det(T0[:3,:3]) <= 0, Lambda not bit-symmetric,
+ * a negative diagonal entry, a non-zero entry in a slot beyond the code length (T0 and code0 of an object without a prior are not looked at).
+ * The one-shot calls have no prior.  (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+int dsp_batch_prior(dsp_batch* b, const float* t_obj_cam0, const float* code0, const double* Lambda);
+/* e (n_objects x (P + 64): e_p | e_c, pose-only: e_c = 0) and chi2 = e^T Lp e (n_objects) at the RETURNED state of the last run -- the
+ * Mahalanobis gate "does the new data contradict the old estimate?".  Host data of the run's one read-back.  NaN for an object that did not
+ * end good, 0 for an object without a prior; an object left out of the partial re-run after a guard trip keeps its values.  Either pointer
+ * may be NULL.  DSP_E_STATE if the last run had no prior. */
+int dsp_batch_prior_fetch(dsp_batch* b, double* e, double* chi2);
+/* Testing (host only, no device): dsp_batch_prior's argument checks for n_objects objects of a batch kind, and ONE object's prior terms
+ * computed on the CPU by the functions the device kernel runs: extra n x (n + 1) = [J^T Lp J | -J^T Lp e], e (P + 64), chi2.  Any output
+ * may be NULL.  dsp_debug_prior_terms returns DSP_E_STATE where the device ends the object DSP_OBJ_NAN. */
+int dsp_debug_prior_check(int pose_only, int code_len, int n_objects, const float* t_obj_cam0, const float* code0, const double* Lambda);
+int dsp_debug_prior_terms(int pose_only, int code_len, const float* t_obj_cam, const float* code, const float* t_obj_cam0, const float* code0,
+                          const double* Lambda, double* extra, double* e, double* chi2);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */

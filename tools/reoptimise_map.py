@@ -25,7 +25,14 @@ iterations each object used are printed: how many a warm start saves depends on 
 
 --posterior FILE.npz writes, for every map object, the posterior record of the run (dsp_batch_posterior, "sum" weights: ids, status, info_pose,
 cov_pose, var_code, loss, M, V, K; objects without an observation have status 1 = none), and prints which objects are poorly constrained.
-The poses and codes written are bit for bit those of a run without the flag.
+The poses and codes written are bit for bit those of a run without the flag.  --posterior-level 2 (default 1) adds what a later run needs to take
+the result back in as a prior: Lambda (71 x 71), g, t_obj_cam, code, and t_world_cam, the camera the record's pose is relative to.
+
+--prior FILE.npz (a file written with --posterior-level 2) fuses those records into this run as a Gaussian prior on each object's pose and code
+(dsp_batch_prior): objects are matched by id, a record that is not ok (or an object without one) gives no prior, and a record taken in another
+camera is re-based (T0 <- T0 t_world_cam_old^-1 t_world_cam_new; the information lives in the object frame and does not change).  A record
+already holds the k3 and k4 terms of its run: re-optimising with the same config counts them twice (include/dsp_gn.h).  The prior's chi2 at
+each result is printed: a large value says the new data contradicts the old estimate.
 """
 import argparse
 import os
@@ -83,14 +90,36 @@ def iterations_histogram(iters):
     return "mean %.2f over %d objects; %s" % (float(iters.mean()), iters.size, ", ".join("%d: %d" % (v, c) for v, c in zip(vals, cnt)))
 
 
-def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None):
+def prior_arrays(prior, objs, obs, idx):
+    """The --prior records matched to the observed objects idx: -> (t_obj_cam0 (n, 4, 4), code0 (n, 64), Lambda (n, 71, 71)); objects without
+    an ok record get Lambda = 0 (no prior).  A record taken in another camera is re-based to the object's current reference camera."""
+    n = len(idx)
+    t0 = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    z0 = np.zeros((n, 64), np.float32)
+    lam = np.zeros((n, 71, 71))
+    row = {int(i): k for k, i in enumerate(np.asarray(prior["ids"]).reshape(-1))}
+    for k, i in enumerate(idx):
+        r = row.get(int(objs[i]["id"]))
+        if r is None or int(prior["status"][r]) != 0:
+            continue
+        rebase = np.linalg.inv(np.asarray(prior["t_world_cam"][r], np.float64)) @ obs[i]["t_world_cam"]
+        t0[k] = (np.asarray(prior["t_obj_cam"][r], np.float64) @ rebase).astype(np.float32)
+        c = np.asarray(prior["code"][r], np.float32).reshape(-1)
+        z0[k, :c.shape[0]] = c
+        lam[k] = prior["Lambda"][r]
+    return t0, z0, lam
+
+
+def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
     tol: None, or (pose_tol, code_tol[, min_iterations]): the per-object convergence rule; stats["iterations_used"] then holds the updates applied
     to every observed object (None without tol).
     posterior: None, "mean" or "sum": stats["posterior"] then holds Batch.posterior()'s level-1 arrays with one row per MAP object (status 1 =
-    none for objects without an observation)."""
+    none for objects without an observation); posterior_level 2 adds Lambda, g, t_obj_cam, code and t_world_cam.
+    prior: None, or the arrays of a level-2 posterior file (ids, status, t_obj_cam, code, Lambda, t_world_cam): prior_arrays;
+    stats["prior_chi2"] then holds e^T Lambda e at each observed object's result (NaN: the object failed)."""
     from dsp_slam_amd import distributed as D
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
@@ -105,6 +134,8 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     parts = [None] * len(shards)
     used = [None] * len(shards)
     post = [None] * len(shards)
+    chi2 = [None] * len(shards)
+    pri = None if prior is None else prior_arrays(prior, objs, obs, idx)
     multiview = any("more_views" in obs[i] for i in idx)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
@@ -113,7 +144,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if (tol is not None or posterior is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None or pri is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -124,12 +155,16 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                 if tol is not None:
                     bt.set_convergence(*tol)
                 if posterior is not None:
-                    bt.set_posterior(1, posterior)
+                    bt.set_posterior(posterior_level, posterior)
+                if pri is not None:
+                    bt.set_prior(pri[0][a:b], pri[1][a:b], pri[2][a:b])
                 bt.run()
                 parts[r] = D.pack_results(*bt.results())
                 used[r] = bt.iterations_used()
                 if posterior is not None:
                     post[r] = bt.posterior()
+                if pri is not None:
+                    chi2[r] = bt.prior_residual()["chi2"]
             finally:
                 bt.close()
             return
@@ -164,15 +199,23 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         n = len(objs)
         records = dict(ids=np.array([o["id"] for o in objs], np.int64), status=np.ones(n, np.int32), info_pose=np.zeros((n, 7, 7)), cov_pose=np.zeros((n, 7, 7)),
                        var_code=np.zeros((n, code_len)), loss=np.zeros(n, np.float32), M=np.zeros(n, np.int64), V=np.zeros(n, np.int64), K=np.zeros(n, np.int64))
+        keys = ("status", "info_pose", "cov_pose", "var_code", "loss", "M", "V", "K")
+        if posterior_level >= 2:
+            records.update(Lambda=np.zeros((n, 71, 71)), g=np.zeros((n, 71)), t_obj_cam=np.zeros((n, 4, 4), np.float32), code=np.zeros((n, code_len), np.float32),
+                           t_world_cam=np.tile(np.eye(4), (n, 1, 1)))
+            keys += ("Lambda", "g", "t_obj_cam", "code")
+            for i in idx:
+                records["t_world_cam"][i] = obs[i]["t_world_cam"]
         k = 0
         for pr in post:
             if pr is None:
                 continue
             m = pr["status"].shape[0]
-            for key in ("status", "info_pose", "cov_pose", "var_code", "loss", "M", "V", "K"):
+            for key in keys:
                 records[key][idx[k:k + m]] = pr[key]
             k += m
-    return out, dict(n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
+    prior_chi2 = None if pri is None else np.concatenate([c for c in chi2 if c is not None] + [np.zeros(0)])
+    return out, dict(prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
                      iterations_used=iters, posterior=records)
 
 
@@ -188,6 +231,10 @@ def main():
                     help="stop each object once its Gauss-Newton step is below these tolerances (pose entries / code entries); off without the flag")
     ap.add_argument("--posterior", default=None, metavar="FILE.npz",
                     help="write every map object's posterior record (pose information / covariance, code variance, loss at the result) of this run")
+    ap.add_argument("--posterior-level", type=int, choices=(1, 2), default=1,
+                    help="2: the --posterior file also holds Lambda, g, the state and the camera of every record -- what --prior reads")
+    ap.add_argument("--prior", default=None, metavar="FILE.npz",
+                    help="fuse the records of an earlier run (written with --posterior FILE.npz --posterior-level 2) into this one as a Gaussian prior")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -200,13 +247,19 @@ def main():
     decoders = [config_decoder(cfg.DeepSDF_DIR).cuda(d) for d in range(n_dev)]        # one decoder (= one handle, one stream) per GPU
     prm = E.params_from_configs(cfg)
     out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute],
-                         tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum")
+                         tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum",
+                         posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)))
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
         st["n_good"], st["n_objects"], st["n_observed"], n_dev, st["seconds"], st["n_observed"] / max(st["seconds"], 1e-9), dst))
     if st["iterations_used"] is not None:
         print("iterations used: %s" % iterations_histogram(st["iterations_used"]))
+    if st["prior_chi2"] is not None:
+        c = st["prior_chi2"]
+        print("prior chi2 at the results: median %.3g, max %.3g over %d objects (%d failed)" % (
+            float(np.nanmedian(c)) if np.isfinite(c).any() else float("nan"), float(np.nanmax(c)) if np.isfinite(c).any() else float("nan"), c.size,
+            int(np.isnan(c).sum())))
     if st["posterior"] is not None:
         rec = st["posterior"]
         np.savez(args.posterior, **rec)

@@ -295,9 +295,12 @@ __global__ __launch_bounds__(256) void k_sample_write(const ObjConst* oc, const 
 // such sample: every term those samples could contribute to the rendered depth (o_l * T_{l-1}), to any suffix sum of T and
 // hence to any kept row is 0 -- their decoder values are never needed.  The forward decoder therefore runs in passes over
 // depth-index ranges [j0, j1), front to back, and a ray drops out after the pass in which it first reports a solid sample.
+// (j0 reaches 64 too: with 64 depth samples, the last adaptive pass of a ray whose pass 0 already covered [0, 64) starts there -- an empty
+// range, not a shift by the word's width)
 __device__ __forceinline__ unsigned long long range_mask(int j0, int j1) {
     const unsigned long long hi = (j1 >= 64) ? ~0ull : ((1ull << j1) - 1ull);
-    return hi & ~((1ull << j0) - 1ull);
+    const unsigned long long lo = (j0 >= 64) ? ~0ull : ((1ull << j0) - 1ull);
+    return hi & ~lo;
 }
 
 // Range of ray gr in the current pass.  Fixed mode (hint == nullptr): [j0, j1) for every ray.  Adaptive mode: pass 0 covers
@@ -614,7 +617,7 @@ __global__ __launch_bounds__(256) void k_tail_tiles(const int4* tiles, int* n_ti
 // ------------------------------------------------------------------------------------------------
 // per-ray occupancy / transmittance scan  (loss.py:84-141)
 // ------------------------------------------------------------------------------------------------
-// One thread per ray, the 50-sample row kept in registers.  Pass 1 (count): occupancy o_j, T_l =
+// One thread per ray, the row of its <= 64 samples (num_depth_samples) kept in registers.  Pass 1 (count): occupancy o_j, T_l =
 // prod_{i<=l}(1-o_i), rendered depth d_u, suffix sums for de_do, keeps samples with |sdf| < th and
 // de_do > 1e-2; stores de_ds per compact sample (0 = dropped), d_u per ray and the kept count.
 // One WAVE per ray, lane = depth index: everything per-sample (occupancy, the two divisions, the keep tests, the compaction) runs in
@@ -704,7 +707,7 @@ __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjStat
     }
 }
 
-// Row compaction: the kept samples of a ray (those with de_ds != 0: typically 2-4 of its <= 50) become jacobian rows, in depth order behind
+// Row compaction: the kept samples of a ray (those with de_ds != 0: typically 2-4 of its <= 64) become jacobian rows, in depth order behind
 // the rows of the rays in front (koff).  One WAVE per ray, lane = position in the ray's compact sample run: one coalesced load finds the kept
 // ones, a ballot places them.
 __global__ __launch_bounds__(256) void k_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff,

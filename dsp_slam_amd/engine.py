@@ -267,16 +267,17 @@ class Batch(object):
                 d[e, i, :row.shape[0]] = row
         L.check(L.load().dsp_batch_debug_depth_schedule(self._h, L.ptr(d), n_it), self.engine._h, "dsp_batch_debug_depth_schedule")
 
-    def debug_samples(self, obj, n_rays, n_depth):
+    def debug_samples(self, obj, n_rays, n_depth, raw_masks=False):
         """(in-sphere mask (n_rays, n_depth) bool, sdf grid, de_ds grid) the last iteration of the last run left for object obj
-        (NaN outside the sphere; de_ds != 0 marks a kept sample)."""
+        (NaN outside the sphere; de_ds != 0 marks a kept sample).  raw_masks: a fourth item, the rays' 64-bit masks as the device holds
+        them (uint64 (n_rays,); bit j = depth index j)."""
         rm = np.zeros(n_rays, np.uint64)
         sdf = np.zeros((n_rays, n_depth), np.float32)
         deds = np.zeros((n_rays, n_depth), np.float32)
         L.check(L.load().dsp_batch_debug_samples(self._h, int(obj), L.ptr(rm, C.POINTER(C.c_uint64)), L.ptr(sdf), L.ptr(deds), sdf.size),
                 self.engine._h, "dsp_batch_debug_samples")
         mask = ((rm[:, None] >> np.arange(n_depth, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        return mask, sdf, deds
+        return (mask, sdf, deds, rm) if raw_masks else (mask, sdf, deds)
 
     def run(self):
         L.check(L.load().dsp_batch_run(self._h), self.engine._h, "dsp_batch_run")

@@ -59,8 +59,8 @@ typedef struct dsp_gn_params {
     float lr;                    /* learning_rate */
     float s_damp;                /* scale_damping */
     int32_t num_iterations;      /* joint_optim.num_iterations */
-    int32_t num_depth_samples;   /* optimizer.num_depth_samples (<= 64) */
-    float cut_off;               /* optimizer.cut_off_threshold */
+    int32_t num_depth_samples;   /* optimizer.num_depth_samples (2 .. 64; DSP_E_ARG otherwise) */
+    float cut_off;               /* optimizer.cut_off_threshold (positive and finite; DSP_E_ARG otherwise) */
     int32_t pose_only_iterations;/* pose_only_optim.num_iterations */
 } dsp_gn_params;
 
@@ -458,7 +458,8 @@ int dsp_debug_prior_terms(int pose_only, int code_len, const float* t_obj_cam, c
 #define DSP_DBG_LP_SMALL_BATCHES 12 /* 1: the low-precision compute mode also on detection-sized batches (automatic: they keep the fp32 latency path, which is faster there) */
 #define DSP_DBG_CLUSTER_FAULT 11    /* value != 0: the following runs' cluster launches lose one workgroup's hand-off (the device-side fallback takes over); 0 also ends the cool-down */
 int dsp_batch_set_debug(dsp_batch* b, int key, int value);
-/* Forensics: front-to-back ranges with explicit depth-index boundaries: bounds[0] = 0 <= ... <= bounds[n_passes] = num_depth_samples. */
+/* Forensics: front-to-back ranges with explicit depth-index boundaries: bounds[0] = 0 <= ... <= bounds[n_passes] = num_depth_samples,
+ * 1 <= n_passes <= num_depth_samples (DSP_E_ARG otherwise); empty ranges are skipped. */
 int dsp_batch_debug_ray_pass_bounds(dsp_batch* b, const int32_t* bounds, int n_passes);
 /* Forensics: start the following runs from the given camera->object matrices (n_objects x 16, used as they are -- no
  * inversion, so a recorded state of the reference can be injected bit for bit) and / or codes (n_objects x 64); NULL t_obj_cam returns

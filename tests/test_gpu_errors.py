@@ -151,6 +151,16 @@ def test_refused_arguments_leave_the_handle_usable(eng):
         eng.reconstruct_batch(E.gn_params(num_depth_samples=65), *_args([o]))
     with pytest.raises(L.DspError):
         eng.reconstruct_batch(E.gn_params(num_depth_samples=1), *_args([o]))
+    # a cut-off that is not positive and finite: sdf_to_occupancy divides by 2 * cut_off (loss_utils.py:40-48)
+    for bad in (0.0, -0.01, np.nan, np.inf):
+        with pytest.raises(L.DspError, match="cut_off"):
+            eng.reconstruct_batch(E.gn_params(cut_off=bad), *_args([o]))
+        with pytest.raises(L.DspError, match="cut_off"):
+            eng.batch(E.gn_params(cut_off=bad), *_args([o]))
+        sampled = np.linspace(1.0, 3.0, 50, dtype=np.float32)
+        with pytest.raises(L.DspError, match=r"failed \(-1\)"):          # DSP_E_ARG
+            eng.compute_render_loss(o["rays"], np.ones(o["rays"].shape[0], np.float32), np.eye(4, dtype=np.float32), sampled, np.zeros(64, np.float32), th=bad)
+    assert np.array_equal(_alone(eng, prm, o)[0], good[0])
     # NULL arguments at the C ABI
     assert lib.dsp_reconstruct_batch(eng._h, C.byref(prm), 1, None, None, None, None, None, None, None, None, None, None, None, None) == -1
     assert lib.dsp_decode_sdf(eng._h, None, None, 4, None) == -1
@@ -159,6 +169,11 @@ def test_refused_arguments_leave_the_handle_usable(eng):
     b = eng.batch(prm, *_args([o]))
     assert lib.dsp_batch_set_debug(b._h, 999, 1) == -1 and lib.dsp_batch_set_debug(b._h, L.DBG_MASK_REUSE, 7) == -1
     assert lib.dsp_batch_set_iterations(b._h, 0) == -1 and lib.dsp_batch_set_prepass(b._h, 3, -1.0) == -1
+    # more explicit pass ranges than depth samples (the launch plan clamps the pass count to D and would run uniform ranges instead)
+    too_many = np.array([0] * 51 + [50], np.int32)
+    assert lib.dsp_batch_debug_ray_pass_bounds(b._h, L.ptr(too_many, L.c_i32p), 51) == -1
+    assert lib.dsp_batch_debug_ray_pass_bounds(b._h, L.ptr(too_many[1:], L.c_i32p), 50) == 0
+    assert lib.dsp_batch_set_ray_passes(b._h, 0) == 0
     # results before the first run: DSP_E_STATE, then the batch still runs
     with pytest.raises(L.DspError, match="not been run"):
         b.results()

@@ -216,9 +216,12 @@ def compare_linearisation(tr, i, its, k4, tol_b=1e-4):
     return False
 
 
-def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0, fp64=True):
+def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0, fp64=True, given_depths=None):
     """(oracle trace on the device's depth samples, the same with the sdf jittered, the oracle's own depth samples[, the fp64
-    linearisation on the first one's sets, its `k4` added]) at object i's state of the device trace tr."""
+    linearisation on the first one's sets, its `k4` added]) at object i's state of the device trace tr.
+    given_depths: the depth samples the run was GIVEN (Batch.set_start_state / set_depth_schedule) instead of deriving them from the pose;
+    they take the third place -- the device's recorded samples are then held against these, and the oracle's own derivation is not run
+    (with two samples the derived range has nothing inside the sphere and the oracle returns no linearisation at all)."""
     o1 = O.GNParams(oprm.k1, oprm.k2, oprm.k3, oprm.k4, oprm.b1, oprm.b2, oprm.lr, oprm.s_damp, 1, oprm.code_len,
                     oprm.num_depth_samples, oprm.cut_off)
     out = []
@@ -227,10 +230,13 @@ def one_iteration_oracle(oracle_decoder, oprm, obj, tr, i=0, fp64=True):
         O.reconstruct_object(oracle_decoder, o1, None, obj["pts"], obj["rays"], obj["depth"], tr["code"][i], trace=otr,
                              t_obj_cam0=tr["t_obj_cam"][i], sdf_jitter=jit, sampled_override=tr["depths"][i])
         out.append(otr[0])
-    otr = []
-    O.reconstruct_object(oracle_decoder, o1, None, obj["pts"], obj["rays"], obj["depth"], tr["code"][i], trace=otr,
-                         t_obj_cam0=tr["t_obj_cam"][i])
-    out.append(otr[0]["depths"])
+    if given_depths is None:
+        otr = []
+        O.reconstruct_object(oracle_decoder, o1, None, obj["pts"], obj["rays"], obj["depth"], tr["code"][i], trace=otr,
+                             t_obj_cam0=tr["t_obj_cam"][i])
+        out.append(otr[0]["depths"])
+    else:
+        out.append(np.asarray(given_depths, np.float32)[:oprm.num_depth_samples].copy())
     if fp64:
         lin = O.linearise_fp64(oracle_decoder, oprm, obj["pts"], obj["rays"], obj["depth"], tr["t_obj_cam"][i], tr["code"][i], tr["depths"][i],
                                out[0]["sets"])
@@ -257,12 +263,15 @@ def explain_flips(eng, prm, oprm, oracle_decoder, obj, tr, code_in=None):
     return flips
 
 
-def _check_iterations(oracle_decoder, obj, traces, oprm, k4, name="", explain=None):
+def _check_iterations(oracle_decoder, obj, traces, oprm, k4, name="", explain=None, fp64=True, given_depths=None):
     """Every iteration strict (identical sets, 1e-4) -- or, where the sets differ, every differing sample named and within round-off of
-    its threshold (explain = (engine, device params); without it a non-strict iteration fails)."""
+    its threshold (explain = (engine, device params); without it a non-strict iteration fails).
+    given_depths[e]: the depth samples the run was GIVEN for iteration e (Batch.set_depth_schedule) instead of deriving them from the pose:
+    the device's recorded samples are then held against these, not against the oracle's own derivation."""
     strict, per_iter, named = 0, [], []
     for e, tr in enumerate(traces):
-        ok = bool(compare_linearisation(tr, 0, one_iteration_oracle(oracle_decoder, oprm, obj, tr), k4))
+        its = one_iteration_oracle(oracle_decoder, oprm, obj, tr, fp64=fp64, given_depths=None if given_depths is None else given_depths[e])
+        ok = bool(compare_linearisation(tr, 0, its, k4))
         strict += ok
         per_iter.append(dict(LAST_LINEARISATION))
         if not LAST_LINEARISATION["same_sets"]:

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "prior_math.h"
+#include "step_rule.h"
 
 namespace dsp {
 
@@ -297,6 +298,28 @@ struct PriorDev {
     int n = 0;                          // 71, pose-only batches 6
 };
 
+// Levenberg-Marquardt step control (dsp_batch_step_control; the rule: step_rule.h), joint batches only.  k_solve<.., STEP = true> keeps one
+// StepObj and one saved system [H | b] (STEP_SYS doubles: 71 rows of 72) per object and writes one log entry per iteration and object.
+constexpr int STEP_SYS = 71 * 72;
+struct StepObj {
+    double F_acc, lambda;       // cost of the accepted state; the damping the next step is solved with
+    float loss_acc;             // ObjState::loss at the accepted state
+    int pad;
+    float t_oc[16];             // the accepted state x_acc
+    float code[CODE_LEN];
+};
+struct StepLogEnt {
+    double cost, lambda;        // F_e; lambda after the decision
+    int decision, pad;          // step_rule::NOT_EVALUATED / ACCEPTED / REJECTED
+};
+struct StepDev {
+    step_rule::Params p{0.0, 0.0, 0.0, 0.0, 0.0};
+    double* sys = nullptr;      // [object][STEP_SYS]
+    StepObj* obj = nullptr;     // [object]
+    StepLogEnt* log = nullptr;  // [iteration][object]
+    int last = 0;               // the run's last iteration: evaluate and decide, apply no step
+};
+
 // kernels_mlp / kernels_gn launchers
 size_t mlp_lds_bytes(int mode);
 void launch_code_bias(const float* codew, const float* b0, const float* blat, const float* codes, int code_stride, float* out, int n_obj, hipStream_t s);
@@ -365,7 +388,8 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 // leader (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
-                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr, const PriorDev* prior = nullptr);    // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr, const PriorDev* prior = nullptr,
+                  const StepDev* step = nullptr);    // step: Levenberg-Marquardt step control, nullptr = off (the kernel without it)   // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
 // the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
 // -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
@@ -379,7 +403,8 @@ void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
                       const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr,
                       const PriorDev* prior = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
-// the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass: e and chi2 at the returned state
+// the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass 1: e and chi2 at the returned
+// state instead; 2 (launch_solve with step control): the terms, and chi2 at the current state in the record's chi2 slot
 void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
 void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,

@@ -1338,11 +1338,14 @@ __global__ __launch_bounds__(64) void k_group_broadcast(const GroupEnt* grp, Obj
 // in a fixed order, no atomics) that k_solve<.., PRIOR = true> adds to its system.  An object without a prior (Lambda all zero) or not GOOD
 // is left alone.  A rotation of T_oc T0^-1 beyond pi - 1e-3 (or a state whose linear part has no positive determinant) ends the object
 // DSP_STATUS_NAN: a prior half a turn away from the state contradicts it.
-// final_pass: the record of the run's read-back instead -- e (P + 64 doubles) and chi2 = e^T Lp e at the RETURNED state; NaN for an object
+// pass_kind 2 (step control): the block as with 0, and chi2 at the CURRENT state in the record's chi2 slot, where k_solve<.., STEP = true>
+// reads its cost's second term (the final pass overwrites it with the returned state's).
+// pass_kind 1 = final_pass: the record of the run's read-back instead -- e (P + 64 doubles) and chi2 = e^T Lp e at the RETURNED state; NaN for an object
 // that did not end good; nothing k_finalize reads is written (no status word either).
 constexpr int PRIOR_THREADS = 256;
-__global__ __launch_bounds__(PRIOR_THREADS) void k_prior_terms(ObjState* st, GnParamsDev prm, PriorDev pr, const GroupEnt* grp, int final_pass) {
+__global__ __launch_bounds__(PRIOR_THREADS) void k_prior_terms(ObjState* st, GnParamsDev prm, PriorDev pr, const GroupEnt* grp, int pass_kind) {
     __shared__ prior_math::Work w;
+    const int final_pass = pass_kind == 1;
     const int b = blockIdx.x, tid = threadIdx.x;
     int ob = b;
     if (grp) {
@@ -1383,6 +1386,7 @@ __global__ __launch_bounds__(PRIOR_THREADS) void k_prior_terms(ObjState* st, GnP
         if (tid == 0) res[prior_math::RES_STRIDE - 1] = prior_math::chi2_of(w, n);
         return;
     }
+    if (pass_kind == 2 && tid == 0) res[prior_math::RES_STRIDE - 1] = prior_math::chi2_of(w, n);
     double* ex = pr.extra + (size_t)ob * n * (n + 1);
     for (int idx = tid; idx < n * (n + 1); idx += PRIOR_THREADS) ex[idx] = prior_math::extra_entry(w, idx / (n + 1), idx % (n + 1), P, n, live, Lp);
 }
@@ -1413,11 +1417,18 @@ template <bool V> struct BoolC { static constexpr bool value = V; };
 // term and in FRONT of the damping, so that H is (Lambda + damping) with the Lambda k_posterior<., true> reports, bit for bit; to b as the
 // last addition.  Entries of rows or columns beyond the decoder's code length are not added.  PRIOR = false is the code of every run without
 // a prior: a template argument like the other two.
-template <bool GROUPS, bool STOP, bool PRIOR>
+// STEP (dsp_batch_step_control; the rule and its reasons: step_rule.h): per-object Levenberg-Marquardt step acceptance.  The state this
+// launch linearised at is a trial: accepted (its [H | b] is saved, plain vector stores by the whole workgroup) or rejected ([H | b] and the
+// parked start state are reloaded from the accepted copy), then (S + lambda I) dx = b is solved and applied to the ACCEPTED state.  On
+// the run's last iteration and on a step that meets the convergence rule no step is applied: the state goes back to x_acc.  No extra LDS
+// (the saved system is read straight into A), no atomics.  Only GROUPS = false is instantiated with it.  STEP = false is the code of
+// every run without the feature.
+template <bool GROUPS, bool STOP, bool PRIOR, bool STEP>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int iter,
                                                          const float* codew, const float* cb0, const float* cblat, float* cbias,
                                                float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj,
-                                               const GroupEnt* grp, const int* gmk, StopRule stop, PriorDev pr) {
+                                               const GroupEnt* grp, const int* gmk, StopRule stop, PriorDev pr, StepDev sd) {
+    static_assert(!(STEP && GROUPS), "step control: joint batches without groups only");
     __shared__ double A[NS1][NS1 + 1];          // [H | b] in rows 0..n-1 (b = column n); b is also kept as ROW n (rows 64 .. 71 are one register of the elimination)
     const int b = blockIdx.x, tid = threadIdx.x;
     if constexpr (GROUPS) { if (grp[b].leader != b) return; }
@@ -1474,6 +1485,16 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         }
     }
     const double g_loss0 = prm.pose_only ? 0.0 : gram(0, 71 * 72 + 71), g_loss1 = prm.pose_only ? 0.0 : gram(1, 71 * 72 + 71);
+    // step control: the object's rule state (iteration 0 has none yet) and, with a prior, chi2 at this state (k_prior_terms, pass kind 2)
+    [[maybe_unused]] double sc_Facc = 0.0, sc_lambda = 0.0, sc_chi2 = 0.0;
+    [[maybe_unused]] float sc_loss_acc = 0.f, sc_loss = 0.f;
+    if constexpr (STEP) {
+        if (iter > 0) { sc_Facc = sd.obj[b].F_acc; sc_lambda = sd.obj[b].lambda; sc_loss_acc = sd.obj[b].loss_acc; }
+        if constexpr (PRIOR) { if (pr_on) sc_chi2 = pr.res[(size_t)b * prior_math::RES_STRIDE + prior_math::RES_STRIDE - 1]; }
+        // the log row of an iteration the object does not evaluate (failed, frozen) reads "not evaluated"; an object left out of a
+        // partial re-run keeps the rows of the run that produced its result
+        if (tid == 0 && status != DSP_STATUS_SKIP) sd.log[(size_t)iter * n_obj + b] = StepLogEnt{0.0, 0.0, step_rule::NOT_EVALUATED, 0};
+    }
     if (status != DSP_STATUS_GOOD) return;
     if (tid < 16) s_toc0[tid] = park;
     if (tid >= 64 && tid < 64 + CODE_LEN) s_code0[tid - 64] = park;
@@ -1484,6 +1505,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         const float ren_loss = (float)g_loss1 / (float)K;
         if (isnan(sdf_loss) || isnan(ren_loss)) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }
         if (tid == 0) s.loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
+        if constexpr (STEP) sc_loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
         float jrot[7], res_rot;
         rotation_prior(pr_tco, pr_scale, jrot, res_rot);
         // only entries 3 and 5 of the prior's jacobian are non-zero; selects instead of a run-time index keep it out of scratch
@@ -1557,6 +1579,32 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
             tr[NSOLVE * NSOLVE + 2 * NSOLVE + 86] = (float)(s.ksum >> 16);
         }
         __syncthreads();
+    }
+    if constexpr (STEP) {
+        // the decision (uniform: every thread holds the same numbers), then the system the step is solved from
+        const double F_e = (double)sc_loss + sc_chi2;
+        double lam = sc_lambda;
+        const int dec = step_rule::decide(iter == 0, F_e, sc_Facc, sd.p, lam);
+        double* sv = sd.sys + (size_t)b * STEP_SYS;
+        StepObj& so = sd.obj[b];
+        if (dec == step_rule::ACCEPTED) {
+            for (int e = tid; e < n * (n + 1); e += SOLVE_THREADS) sv[e] = A[e / (n + 1)][e % (n + 1)];
+            if (tid < 16) so.t_oc[tid] = s_toc0[tid];
+            if (tid >= 64 && tid < 64 + CODE_LEN) so.code[tid - 64] = s_code0[tid - 64];
+            if (tid == 0) { so.F_acc = F_e; so.loss_acc = sc_loss; }
+        } else {
+            for (int e = tid; e < n * (n + 1); e += SOLVE_THREADS) A[e / (n + 1)][e % (n + 1)] = sv[e];
+            if (tid < 16) s_toc0[tid] = so.t_oc[tid];
+            if (tid >= 64 && tid < 64 + CODE_LEN) s_code0[tid - 64] = so.code[tid - 64];
+            if (tid == 0) s.loss = sc_loss_acc;           // the loss AT the state the object keeps
+        }
+        if (tid == 0) {
+            so.lambda = lam;
+            sd.log[(size_t)iter * n_obj + b] = StepLogEnt{F_e, lam, dec, 0};
+        }
+        __syncthreads();
+        // lambda on the diagonal of the live unknowns, behind everything else (0 adds nothing); the elimination's first barrier follows
+        if (lam != 0.0 && tid < pd + prm.code_len) A[tid][tid] += lam;
     }
     {
         // 2. H dx = b by elimination in fp64.  H = sum w J^T J + positive diagonal is symmetric (bit for bit: the Gram kernel's fmaf chains
@@ -1692,9 +1740,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         if (s_sing) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }      // uniform
         __syncthreads();
     }
+    if constexpr (!STEP) {
     if (trace) {
         float* tr = trace + ((size_t)iter * n_obj + b) * TRACE_STRIDE;
         for (int e = tid; e < n; e += SOLVE_THREADS) tr[NSOLVE * NSOLVE + NSOLVE + e] = (float)A[e][n];
+    }
     }
     // the convergence rule, on the step the update below applies (lr dx; pose-only: dx): thread i < n holds entry i
     bool stop_now = false;
@@ -1706,13 +1756,26 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         }
         stop_now = __syncthreads_and(ok) && iter + 1 >= stop.min_iterations;
     }
+    // step control: no step on the run's last iteration or on a step that meets the rule -- dx reads zero (the trace row too) and the
+    // update below puts the object back to x_acc, with everything the front of an iteration derives from it
+    [[maybe_unused]] bool no_step = false;
+    if constexpr (STEP) {
+        no_step = sd.last != 0 || stop_now;
+        if (no_step && tid < n) A[tid][n] = 0.0;          // (each entry was last read by this very thread)
+        __syncthreads();
+        if (trace) {
+            float* tr = trace + ((size_t)iter * n_obj + b) * TRACE_STRIDE;
+            for (int e = tid; e < n; e += SOLVE_THREADS) tr[NSOLVE * NSOLVE + NSOLVE + e] = (float)A[e][n];
+        }
+    }
     // 3. update (optimizer.py:187-192 / 73-74).  Wave 0 carries the pose (one lane: exp map, 4x4 product, the next iteration's derived
     //    state -- a few us of serial fp64), wave 1 the code, and waves 2.. the next iteration's code bias once the code is in LDS: the
     //    serial pose work no longer sits in front of the bias loop.
     __shared__ float zc[CODE_LEN];
     if (!prm.pose_only && tid >= 64 && tid < 64 + CODE_LEN) {
         const int i = tid - 64;
-        const float zv = s_code0[i] + prm.lr * (float)A[pd + i][n];
+        float zv = s_code0[i] + prm.lr * (float)A[pd + i][n];
+        if constexpr (STEP) { if (no_step) zv = s_code0[i]; }
         s.code[i] = zv;
         zc[i] = zv;
         // the prepass margin follows the code (this wave holds all CODE_LEN = 64 entries)
@@ -1738,6 +1801,12 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
                 for (int k = 0; k < 4; ++k) acc += dT[4 * r + k] * s_toc0[4 * k + cc];
                 nt[4 * r + cc] = acc;
             }
+        if constexpr (STEP) {
+            if (no_step) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) nt[i] = s_toc0[i];
+            }
+        }
         if (tid == 0) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) s.t_oc[i] = nt[i];
@@ -2182,22 +2251,29 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 }
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
-                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior) {
+                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior, const StepDev* step) {
+    const StepDev sd = step ? *step : StepDev{};
     const StopRule rule = stop ? *stop : StopRule{0.0, 0.0, 1};
     const PriorDev pr = prior ? *prior : PriorDev{};
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
     if (!grp) {
-        if (prior) launch_prior_terms(st, prm, pr, nullptr, 0, B, s);
-        auto k = prior ? (stop ? k_solve<false, true, true> : k_solve<false, false, true>) : (stop ? k_solve<false, true, false> : k_solve<false, false, false>);
+        if (prior) launch_prior_terms(st, prm, pr, nullptr, step ? 2 : 0, B, s);
+        auto k = prior ? (stop ? k_solve<false, true, true, false> : k_solve<false, false, true, false>)
+                       : (stop ? k_solve<false, true, false, false> : k_solve<false, false, false, false>);
+        if (step)
+            k = prior ? (stop ? k_solve<false, true, true, true> : k_solve<false, false, true, true>)
+                      : (stop ? k_solve<false, true, false, true> : k_solve<false, false, false, true>);
         hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr);
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr, sd);
         return;
     }
     hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B);
     if (prior) launch_prior_terms(st, prm, pr, grp, 0, B, s);
-    auto k = prior ? (stop ? k_solve<true, true, true> : k_solve<true, false, true>) : (stop ? k_solve<true, true, false> : k_solve<true, false, false>);
+    if (step) throw std::invalid_argument("step control is not built for multi-view batches");
+    auto k = prior ? (stop ? k_solve<true, true, true, false> : k_solve<true, false, true, false>)
+                   : (stop ? k_solve<true, true, false, false> : k_solve<true, false, false, false>);
     hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
-                       (const int*)gmk, rule, pr);
+                       (const int*)gmk, rule, pr, sd);
     launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
 }
 void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s) {

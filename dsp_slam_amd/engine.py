@@ -124,6 +124,26 @@ class Batch(object):
         L.check(L.load().dsp_batch_iterations_used(self._h, L.ptr(out, L.c_i32p)), self.engine._h, "dsp_batch_iterations_used")
         return out
 
+    # ---- Levenberg-Marquardt step control (dsp_batch_step_control, include/dsp_gn.h; the rule: csrc/step_rule.h) ---------------------------
+    def set_step_control(self, lambda0=0.0, up=10.0, down=0.1, lambda_min=1.0, lambda_max=float("inf")):
+        """Keep an iteration's state only if it lowers the cost (loss, + the prior's chi2): a rejected trial is discarded and the accepted
+        state's system is solved again with lambda <- min(max(lambda, lambda_min) * up, lambda_max) on its diagonal; an acceptance multiplies
+        lambda by down.  The run's last iteration only evaluates, so the returned state is the best evaluated one and `loss` is the loss at it.
+        The defaults are NOT measurements: 10 and 0.1 are Marquardt's conventional factors, lambda_min = 1 is the size of the reference's
+        own pose damping (+ I), and lambda0 = 0 makes the first step the reference's.  set_step_control(0, 0, 0, 0, 0) = off, the initial
+        state.  Joint batches only."""
+        L.check(L.load().dsp_batch_step_control(self._h, float(lambda0), float(up), float(down), float(lambda_min), float(lambda_max)),
+                self.engine._h, "dsp_batch_step_control")
+
+    def step_log(self):
+        """The last run's decisions (dsp_batch_step_log): dict(decision int32 (iterations, n) -- 0 not evaluated (failed / frozen / left out),
+        1 accepted, 2 rejected; cost float64 (iterations, n) = F_e; lambda float64 (iterations, n) = the value after the decision)."""
+        shape = (self.iters, self.n)
+        out = {"decision": np.zeros(shape, np.int32), "cost": np.zeros(shape), "lambda": np.zeros(shape)}
+        L.check(L.load().dsp_batch_step_log(self._h, L.ptr(out["decision"], L.c_i32p), L.ptr(out["cost"], L.c_f64p), L.ptr(out["lambda"], L.c_f64p)),
+                self.engine._h, "dsp_batch_step_log")
+        return out
+
     # ---- posterior (changes no result: one more linearisation at the returned state, include/dsp_gn.h) ------------------------------------
     def set_posterior(self, level=1, weights="mean"):
         """level 0 = off (initial), 1 = pose information / covariance, code variance, loss and counts per object, 2 = also Lambda, g and the
@@ -343,10 +363,22 @@ def _posterior_args(posterior):
     return 1, posterior
 
 
-def _run_resident(b, convergence, posterior, prior):
+def _step_control_args(step_control):
+    """step_control= of the Engine calls and of the Optimizer's config: True (Batch.set_step_control's defaults), a dict of its keyword
+    arguments, or a (lambda0, up, down, lambda_min, lambda_max) tuple -> keyword arguments."""
+    if step_control is True:
+        return {}
+    if isinstance(step_control, dict):
+        return dict(step_control)
+    return dict(zip(("lambda0", "up", "down", "lambda_min", "lambda_max"), step_control))
+
+
+def _run_resident(b, convergence, posterior, prior, step_control=None):
     """The optional rules of the Engine's one-call forms on a resident batch: -> results() [+ (posterior(),)] [+ (prior_residual(),)]."""
     if convergence is not None:
         b.set_convergence(*convergence)
+    if step_control is not None and step_control is not False:
+        b.set_step_control(**_step_control_args(step_control))
     if posterior is not None:
         b.set_posterior(*_posterior_args(posterior))
     if prior is not None:
@@ -720,13 +752,16 @@ class Engine(object):
         set_start_state(t_obj_cam) work on it; results()[0] is estimate_pose_batch's output, bit for bit."""
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
-    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, posterior=None, prior=None):
+    def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, step_control=None, posterior=None,
+                          prior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
         convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
         posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
         (the first four are bit for bit those of the call without it).
         prior: None, or dict(t_obj_cam, code, Lambda) / (t_obj_cam0, code0, Lambda) of per-object arrays -- Batch.set_prior; the call then
-        returns Batch.prior_residual() as its LAST item (behind the posterior, where both are asked for)."""
+        returns Batch.prior_residual() as its LAST item (behind the posterior, where both are asked for).
+        step_control: None (off), True (the defaults), a dict of Batch.set_step_control's keyword arguments or a (lambda0, up, down,
+        lambda_min, lambda_max) tuple; the returned items are the same, `loss` is then the loss AT the returned state."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
             return empty + (() if posterior is None else ({},)) + (() if prior is None else ({},))
@@ -734,7 +769,7 @@ class Engine(object):
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
-            return _run_resident(b, convergence, posterior, prior)
+            return _run_resident(b, convergence, posterior, prior, step_control)
         finally:
             b.close()
 

@@ -85,6 +85,25 @@ class Optimizer(object):
                 self.posterior_pose_only = optional_weights(optim_cfg["pose_only_optim"], "pose_only_optim")
         except TypeError:
             pass
+        # ADDITION (not in the reference's configs): "step_control" under "joint_optim" switches Levenberg-Marquardt step control on
+        # (dsp_batch_step_control): true (Batch.set_step_control's defaults), a dict of its keyword arguments, or a list [lambda0, up, down,
+        # lambda_min, lambda_max].  Read with a membership test like the keys above; absent or false means off.  Single-view joint runs only
+        # (reconstruct_object / reconstruct_objects): a multi-view batch has no step control.
+        try:
+            sc = joint["step_control"] if "step_control" in joint else None
+        except TypeError:
+            sc = None
+        if sc is not None and sc is not False and sc is not True:
+            allowed = ("lambda0", "up", "down", "lambda_min", "lambda_max")
+            if hasattr(sc, "keys"):
+                sc = {k: float(sc[k]) for k in sc.keys()}
+                if not set(sc) <= set(allowed):
+                    raise ValueError("optimizer.joint_optim.step_control takes the keys %s (got %r)" % (", ".join(allowed), sorted(sc)))
+            else:
+                sc = tuple(float(v) for v in sc)
+                if len(sc) != 5:
+                    raise ValueError("optimizer.joint_optim.step_control as a list is [lambda0, up, down, lambda_min, lambda_max]")
+        self.step_control_joint = None if sc is None or sc is False else sc
 
     def _params(self):
         return _engine.gn_params(self.k1, self.k2, self.k3, self.k4, self.b1, self.b2, self.lr, self.s_damp,
@@ -146,6 +165,8 @@ class Optimizer(object):
             kw["posterior"] = self.posterior_joint
         if priors is not None:
             kw["prior"] = self._stack_priors(priors, 71, self.code_len)
+        if self.step_control_joint is not None:
+            kw["step_control"] = self.step_control_joint
         res = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
             [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)

@@ -442,6 +442,43 @@ int dsp_debug_prior_check(int pose_only, int code_len, int n_objects, const floa
 int dsp_debug_prior_terms(int pose_only, int code_len, const float* t_obj_cam, const float* code, const float* t_obj_cam0, const float* code0,
                           const double* Lambda, double* extra, double* e, double* chi2);
 
+/* ---- Levenberg-Marquardt step control (opt-in, joint batches) ---------------------------------------------------------------------------
+ * The reference's iteration has FIXED damping and does not settle: it passes through states several times better than the one it
+ * returns (profiles/early_stop.md: the step "wanders").  With step control every iteration's state is a TRIAL that is kept only if it
+ * lowers the cost; the rule lives in csrc/step_rule.h, on the device inside the solve step, with no host round trip.  Per object:
+ *     cost       F_e = (double) loss_e (float32 k1 L_render + k2 L_sdf, the result row's `loss`), + the prior's chi2 at x_e with a prior on.
+ *                The k3 and k4 terms are NOT part of it: the k4 term (1e7) has a zero jacobian on the reference's exact-upright branch, so
+ *                the first step tilts freely and a cost with k4 in it rejects the steps that lower the loss.
+ *     e == 0     accept; lambda = lambda0
+ *     F_e < F_acc (strict, false for NaN): accept; lambda <- lambda * down
+ *     otherwise  reject; lambda <- min(max(lambda, lambda_min) * up, lambda_max)
+ *     accept     x_acc <- x_e, F_acc <- F_e, and [H | b] as assembled (the reference's damping and a prior's block included) is saved
+ *     reject     [H | b] is reloaded from the saved copy, the trial and its linearisation are discarded
+ *     step       (S + lambda I) dx = b, lambda added in fp64 to the diagonal of the live unknowns behind everything else (lambda = 0 leaves
+ *                the bits of the system alone); the update exp(lr dx) x_acc and everything derived from it follow as without the rule
+ * NO step is applied on the run's last iteration, nor on an iteration whose solved step meets the convergence rule (dsp_batch_convergence,
+ * evaluated on that step): the object is put back to (frozen at) x_acc.  So a run of N iterations makes N linearisations and at most
+ * N - 1 steps, the returned state is the best EVALUATED state, and the returned loss is the loss AT that state (without step control it is
+ * one update older).  dsp_batch_iterations_used counts the iterations the object evaluated.  Trace rows record the linearisation at the
+ * state the iteration evaluated and the dx it solved (zeros when no step was applied).  A trial state at which the object fails by the
+ * reference's rules (< 10 in-sphere samples, K == 0, NaN, singular solve, underivable pose) fails the object as in a run without step
+ * control; turning that into a rejection is not built.  The partial re-run after a prepass-guard trip starts the rule afresh for the
+ * objects it re-runs.  Works with the convergence rule, the posterior (it linearises at the returned state), the prior and either compute
+ * mode.  All five arguments zero = off, the initial state: such a run launches the kernels of a batch that never had it and returns the
+ * same bits.  The saved systems (~41 KB per object) are allocated the first time the feature is enabled.
+ * DSP_E_ARG (the previous setting stays): a non-finite value (lambda_max may be +inf), lambda0 < 0, up <= 1, down <= 0 or > 1,
+ * lambda_min <= 0, lambda_max < lambda_min, a pose-only batch (the inlier filter changes the point set at iteration 4: costs are not
+ * comparable across it), a multi-view batch.  The one-shot calls have no step control.  (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+int dsp_batch_step_control(dsp_batch* b, double lambda0, double up, double down, double lambda_min, double lambda_max);
+/* The last run's decisions: decision 0 not evaluated (failed / frozen / left out), 1 accepted, 2 rejected; cost = F_e; lambda = the value
+ * after the decision.  n_iterations x n_objects each (iteration-major), host data of the run's one read-back; any pointer may be NULL.
+ * An object left out of the partial re-run after a guard trip keeps its rows.  DSP_E_STATE if the last run had no step control. */
+int dsp_batch_step_log(dsp_batch* b, int32_t* decision, double* cost, double* lambda);
+/* Testing (host only, no device): the rule of csrc/step_rule.h applied to a cost sequence of n entries (the function the device runs),
+ * and dsp_batch_step_control's argument checks (DSP_E_ARG; the all-zero "off" setting is no rule: DSP_E_ARG too).  Outputs may be NULL. */
+int dsp_debug_step_rule(int32_t n, const double* cost, double lambda0, double up, double down, double lambda_min, double lambda_max,
+                        int32_t* decision, double* lambda);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */

@@ -33,6 +33,10 @@ the result back in as a prior: Lambda (71 x 71), g, t_obj_cam, code, and t_world
 camera is re-based (T0 <- T0 t_world_cam_old^-1 t_world_cam_new; the information lives in the object frame and does not change).  A record
 already holds the k3 and k4 terms of its run: re-optimising with the same config counts them twice (include/dsp_gn.h).  The prior's chi2 at
 each result is printed: a large value says the new data contradicts the old estimate.
+
+--step-control L0 UP DOWN LMIN LMAX (off without the flag) switches Levenberg-Marquardt step control on (dsp_batch_step_control): a state is
+kept only if it lowers the loss, a rejected step is solved again with more damping, and the loss written is the loss AT the returned state.
+Conventional values: 0 10 0.1 1 inf.  The accepted / rejected counts are printed.  Not for maps with multi-view objects.
 """
 import argparse
 import os
@@ -110,7 +114,8 @@ def prior_arrays(prior, objs, obs, idx):
     return t0, z0, lam
 
 
-def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None):
+def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None,
+               step_control=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
@@ -119,7 +124,9 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     posterior: None, "mean" or "sum": stats["posterior"] then holds Batch.posterior()'s level-1 arrays with one row per MAP object (status 1 =
     none for objects without an observation); posterior_level 2 adds Lambda, g, t_obj_cam, code and t_world_cam.
     prior: None, or the arrays of a level-2 posterior file (ids, status, t_obj_cam, code, Lambda, t_world_cam): prior_arrays;
-    stats["prior_chi2"] then holds e^T Lambda e at each observed object's result (NaN: the object failed)."""
+    stats["prior_chi2"] then holds e^T Lambda e at each observed object's result (NaN: the object failed).
+    step_control: None, or (lambda0, up, down, lambda_min, lambda_max) -- Batch.set_step_control; stats["step_decisions"] then holds
+    (accepted, rejected) counted over all observed objects and iterations."""
     from dsp_slam_amd import distributed as D
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
@@ -137,6 +144,9 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     chi2 = [None] * len(shards)
     pri = None if prior is None else prior_arrays(prior, objs, obs, idx)
     multiview = any("more_views" in obs[i] for i in idx)
+    if multiview and step_control is not None:
+        raise ValueError("step control does not take multi-view objects")
+    steps = [None] * len(shards)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
 
@@ -144,7 +154,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if (tol is not None or posterior is not None or pri is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None or pri is not None or step_control is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -158,7 +168,12 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                     bt.set_posterior(posterior_level, posterior)
                 if pri is not None:
                     bt.set_prior(pri[0][a:b], pri[1][a:b], pri[2][a:b])
+                if step_control is not None:
+                    bt.set_step_control(*step_control)
                 bt.run()
+                if step_control is not None:
+                    dec = bt.step_log()["decision"]
+                    steps[r] = (int((dec == 1).sum()), int((dec == 2).sum()))
                 parts[r] = D.pack_results(*bt.results())
                 used[r] = bt.iterations_used()
                 if posterior is not None:
@@ -215,7 +230,8 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                 records[key][idx[k:k + m]] = pr[key]
             k += m
     prior_chi2 = None if pri is None else np.concatenate([c for c in chi2 if c is not None] + [np.zeros(0)])
-    return out, dict(prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
+    step_decisions = None if step_control is None else tuple(int(sum(x[k] for x in steps if x is not None)) for k in (0, 1))
+    return out, dict(step_decisions=step_decisions, prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
                      iterations_used=iters, posterior=records)
 
 
@@ -235,6 +251,8 @@ def main():
                     help="2: the --posterior file also holds Lambda, g, the state and the camera of every record -- what --prior reads")
     ap.add_argument("--prior", default=None, metavar="FILE.npz",
                     help="fuse the records of an earlier run (written with --posterior FILE.npz --posterior-level 2) into this one as a Gaussian prior")
+    ap.add_argument("--step-control", type=float, nargs=5, metavar=("L0", "UP", "DOWN", "LMIN", "LMAX"), default=None,
+                    help="Levenberg-Marquardt step control: keep a state only if it lowers the loss (conventional: 0 10 0.1 1 inf); off without the flag")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -248,13 +266,16 @@ def main():
     prm = E.params_from_configs(cfg)
     out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute],
                          tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum",
-                         posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)))
+                         posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)),
+                         step_control=None if args.step_control is None else tuple(args.step_control))
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
         st["n_good"], st["n_objects"], st["n_observed"], n_dev, st["seconds"], st["n_observed"] / max(st["seconds"], 1e-9), dst))
     if st["iterations_used"] is not None:
         print("iterations used: %s" % iterations_histogram(st["iterations_used"]))
+    if st["step_decisions"] is not None:
+        print("step control: %d states accepted, %d rejected" % st["step_decisions"])
     if st["prior_chi2"] is not None:
         c = st["prior_chi2"]
         print("prior chi2 at the results: median %.3g, max %.3g over %d objects (%d failed)" % (

@@ -65,8 +65,6 @@ struct MlpArgs {
     const float4* pts;          // object-frame points (xyz, w unused)
     const int* index;           // forward kernel, optional: point i of a tile is pts[index[first + i]] and its sdf goes to
                                 // out_sdf[index[first + i]] (front-to-back ray passes evaluate a subset of the sample list)
-    const float* codes;         // code of object o at codes + o * code_stride
-    int code_stride;            // in floats (multiple of 4)
     const float* code_bias;     // per object: [0..511] = W0[:, :64] code + b0, [512..1023] = W_lat[:, code cols] code + b_lat
     int code_bias_stride;       // in floats (multiple of 4)
     unsigned short* mask_buf;   // MODE 1 writes / MODE 3 reads: [sample][lane group 4][layer 8][output group 8] relu bits (16 per word)
@@ -100,7 +98,7 @@ struct MlpArgs {
     unsigned cl_epoch_base;     //   counter value this launch starts from (the host advances it by CL_EPOCH_STRIDE per launch)
     int cl_fault;               //   fault injection (tests): workgroup 3 of every cluster never publishes -> its siblings' bounded spins run out
     int cluster_max_tiles;      //   the cluster kernel runs lists of up to this many tiles ...
-    int split_min_tiles;        //   ... and the latency form (mlp_split_kernel<true>) lists of at least this many (0 = always)
+    int split_min_tiles;        //   ... and the latency form (mlp_split_kernel<2>) lists of at least this many (0 = always)
     DirectTiles direct;         // one-object batches: no tile list (kind != 0)
 };
 constexpr unsigned CL_SPIN_TICKS_DEFAULT = 200000;   // 2 ms: ~500 healthy hand-offs of ~3.5 us

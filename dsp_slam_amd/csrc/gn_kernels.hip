@@ -590,7 +590,7 @@ __global__ __launch_bounds__(256) void k_build_tiles(const ObjConst* oc, ObjStat
 
 // Tail split of a forward tile list (latency-sized batches): a launch of T 64-point tiles on n_cu CUs takes ceil(T / n_cu) rounds of
 // one tile time each, and the last round is often nearly empty (one cfg2 object: 312 band tiles = one full round + 56).  When that
-// remainder is at most half a round, its tiles are re-listed as 16-point tiles for the latency-form kernel (mlp_split_kernel<false>,
+// remainder is at most half a round, its tiles are re-listed as 16-point tiles for the latency-form kernel (mlp_split_kernel<0 / 1>,
 // ~0.3 of a 64-point tile's time, bit-identical results), which runs them in a launch of its own: the 64-point launch loses its
 // last round.  tiles16 needs 4 * (n_cu / 2) entries.
 __global__ __launch_bounds__(256) void k_tail_tiles(const int4* tiles, int* n_tiles, int4* tiles16, int* n_tiles16, int n_cu) {

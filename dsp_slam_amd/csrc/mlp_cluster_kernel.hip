@@ -28,12 +28,12 @@
 // takes the list when the word is set -- the same iteration's rows are recomputed one workgroup per tile, nothing is discarded or
 // repeated by the host, and the cluster launches of the run's remaining iterations return at entry.  A shared GPU (SLAM's detectors
 // run on it from another thread, Tracking_util.cc:31-57) that keeps a member from being scheduled therefore costs <= a few ms once.
-// Same k order, same bias seeding, same relu masks per output element as mlp_kernel<2> / mlp_split_kernel<true>: bit-identical
-// gradients (tests/test_gpu_round4.py::test_cluster_kernel_is_exact).
+// Same k order, same bias seeding, same relu masks per output element as mlp_kernel<2> / mlp_split_kernel<2> -- the tile steps are the
+// same code (mlp_common.h): bit-identical gradients (tests/test_gpu_round4.py::test_cluster_kernel_is_exact).
 //
 // Weights: the wave's rows only, as its own stream (`wcluster`: for every pass the chunks of its two row tiles, two k-steps per 16-byte
-// lane element), through a private LDS ring of 5 x 4 KiB by LDS-DMA -- the latency form's protocol with "k-step" read as "pair of
-// k-steps": one ds_read_b128 and one DMA piece per four MFMAs.
+// lane element), through a private LDS ring of 5 x 4 KiB by LDS-DMA -- the latency form's ring (WaveRing, mlp_common.h) with a pair of
+// k-steps as its step: one ds_read_b128 and one DMA piece per four MFMAs.
 //
 // Replaces get_batch_sdf_jacobian (reconstruct/loss_utils.py:82-103) for detection-sized launches.
 #include "dsp_internal.h"
@@ -79,36 +79,18 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
     const int u = 4 * rank + wave;              // wave slot in the cluster: row tiles 2u, 2u+1 of every layer
     const int og = u >> 1, half = u & 1;        // ... = tiles 2 half, 2 half + 1 of 64-row output group og
 
-    float* bias_l = reinterpret_cast<float*>(smem);
-    float* cb_l = reinterpret_cast<float*>(smem + BIAS_BYTES);
-    unsigned short* mask_l = reinterpret_cast<unsigned short*>(smem + BIAS_BYTES + CODEBIAS_BYTES);
-    f32x4* xch = reinterpret_cast<f32x4*>(smem + BIAS_BYTES + CODEBIAS_BYTES + CL_MASK_BYTES);
-    char* ring_ptr = smem + BIAS_BYTES + CODEBIAS_BYTES + CL_MASK_BYTES + CL_XCH_BYTES + wave * (CL_SNB * CL_MINI);
-    const unsigned ring0 = lds_addr(ring_ptr);
+    const DecoderLds lds = carve_lds(smem);
+    float* const bias_l = lds.bias;
+    float* const cb_l = lds.cb;
+    unsigned short* const mask_l = lds.mask;
+    f32x4* xch = reinterpret_cast<f32x4*>(smem + LDS_HEAD_BYTES + CL_MASK_BYTES);
 
-    for (int i = tid; i < a.n_bias_rows * WIDTH; i += 256) bias_l[i] = a.bias_tab[i];
-    __syncthreads();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_bias_table(a, bias_l, tid);
 
     // ---- this wave's weight stream (wave-uniform state) -----------------------------------------------------------------
-    const int total_minis = a.cl_len[u];
-    const char* wbase = reinterpret_cast<const char*>(a.wcluster) + (size_t)a.cl_off[u] * CL_MINI;
-    const unsigned lane_off = lane * 16;
-    int issue_pos = 0, issue_slot = 0, rd_slot = 0;
-    const char* isrc = wbase;
-    unsigned idst = ring0;
-    auto issue_next = [&]() {
-        issue_pos = (issue_pos + 1 == total_minis) ? 0 : issue_pos + 1;
-        issue_slot = (issue_slot + 1 == CL_SNB) ? 0 : issue_slot + 1;
-        isrc = wbase + (size_t)issue_pos * CL_MINI;
-        idst = ring0 + issue_slot * CL_MINI;
-    };
-#pragma unroll
-    for (int i = 0; i < CL_SNB - 1; ++i) { glds_quarter(isrc, lane_off, idst); issue_next(); }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (CL_SNB - 2)) : "memory");     // mini-chunk 0 has landed
-    f32x4 abuf[4];        // A operands of k-step pairs, read two pairs ahead
-    abuf[0] = *reinterpret_cast<const f32x4*>(ring_ptr + lane * 16);
-    abuf[1] = *reinterpret_cast<const f32x4*>(ring_ptr + lane * 16 + 1024);
+    WaveRing<CL_SNB, CL_MINI> ring;
+    ring.prime(reinterpret_cast<const char*>(a.wcluster) + (size_t)a.cl_off[u] * CL_MINI,
+               smem + LDS_HEAD_BYTES + CL_MASK_BYTES + CL_XCH_BYTES + wave * (CL_SNB * CL_MINI), lane, a.cl_len[u], 0);
 
     // ---- the cluster's exchange buffers and counters ----------------------------------------------------------------------
     // (descriptors from kernel arguments and blockIdx only: wave-uniform by construction)
@@ -122,8 +104,6 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
 #pragma unroll
     for (int i = 0; i < 128; ++i) sin_[i] = 0.f;
     acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     // One hand-off round the cluster.  pub[0], pub[1]: this wave's row tiles 2u, 2u + 1 (published when `publish`).  Tile t takes part in
     // the exchange when t < n_lo or t >= hi_from (ordinary passes: the layer's 4 * nog row tiles and hi_from = 32; the final hand-off:
@@ -224,33 +204,24 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
         float4 pt = a.pts[pidx];
         if (!valid) pt = make_float4(0.f, 0.f, 0.f, 0.f);
         lds_barrier();        // previous tile's readers of cb_l are done
-        reinterpret_cast<float4*>(cb_l)[tid] = reinterpret_cast<const float4*>(a.code_bias + (size_t)td.z * a.code_bias_stride)[tid];
+        stage_code_bias(a, cb_l, td.z, tid);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();
         {   // layer 0 on the VALU, redundantly in every wave (the slab is needed everywhere); masks of the own tiles only
-            const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
 #pragma unroll
             for (int t = 0; t < 32; ++t) {
-                const int row = 16 * t;
-                const f32x4 c0 = *reinterpret_cast<const f32x4*>(cb_l + row + 4 * g);
-                const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + row);
-                const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + row);
-                const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + row);
+                const f32x4 pre = layer0_rows(a, bias_l, cb_l, g, 16 * t, pt);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) sin_[4 * t + r] = fmaf(wz[r], pt.z, fmaf(wy[r], pt.y, fmaf(wx[r], pt.x, c0[r])));
+                for (int r = 0; r < 4; ++r) sin_[4 * t + r] = pre[r];
             }
-            // relu masks of the own two tiles: the same fmaf chains once more, addressed by the wave slot (selecting them out of the
+            // relu masks of the own two tiles: the same rows once more, addressed by the wave slot (selecting them out of the
             // 128 registers by a run-time tile index costs ~270 registers of live ranges: measured, 67 spills)
             unsigned bits = 0;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int row = 16 * (2 * u + j);
-                const f32x4 c0 = *reinterpret_cast<const f32x4*>(cb_l + row + 4 * g);
-                const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + row);
-                const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + row);
-                const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + row);
+                const f32x4 pre = layer0_rows(a, bias_l, cb_l, g, 16 * (2 * u + j), pt);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) bits |= (fmaf(wz[r], pt.z, fmaf(wy[r], pt.y, fmaf(wx[r], pt.x, c0[r]))) > 0.f ? 1u : 0u) << (4 * j + r);
+                for (int r = 0; r < 4; ++r) bits |= mask_bit(pre[r], 4 * j + r);
             }
             mask_l[0 * 256 + tid] = (unsigned short)bits;
 #pragma unroll
@@ -264,38 +235,14 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
         for (int ps = 0; ps < a.n_pass; ++ps) {
             const PassDesc pd = a.pass[ps];
             const bool mine = og < pd.nog;
-            if (pd.kind == 2) {
-                // (row 445 = tile 27, row 477 = tile 29 with 32-D codes; both are row 13 of their tile: lane group 3, registers 1..3)
-                if (g == 3) {
-                    if (a.lat_tile == 29) { sin_[117] = pt.x; sin_[118] = pt.y; sin_[119] = pt.z; }
-                    else { sin_[109] = pt.x; sin_[110] = pt.y; sin_[111] = pt.z; }
-                }
-            } else if (pd.kind == 5) {
-                const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
-                float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + 16 * t);
-                    const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + 16 * t);
-                    const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + 16 * t);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        gx = fmaf(wx[r], sin_[4 * t + r], gx);
-                        gy = fmaf(wy[r], sin_[4 * t + r], gy);
-                        gz = fmaf(wz[r], sin_[4 * t + r], gz);
-                    }
-                }
-                gx += __shfl_xor(gx, 16); gx += __shfl_xor(gx, 32);
-                gy += __shfl_xor(gy, 16); gy += __shfl_xor(gy, 32);
-                gz += __shfl_xor(gz, 16); gz += __shfl_xor(gz, 32);
-                gfirst = (g == 0) ? gx : (g == 1) ? gy : gz;
-            }
+            if (pd.kind == 2) reinject_xyz(sin_, g, a.lat_tile, pt);
+            else if (pd.kind == 5) gfirst = first_layer_xyz_grad(a, bias_l, g, sin_);
 
             // ---- this wave's two row tiles: nchunks x 8 k-step pairs, four MFMAs per pair ---------------------------------------
             if (mine) {
                 f32x4 bias2[2];
                 if (pd.bias_row != -1) {
-                    const float* bp = (pd.bias_row == -2 ? cb_l + WIDTH : bias_l + pd.bias_row * WIDTH) + 32 * u + 4 * g;
+                    const float* bp = pass_bias_vec(pd.bias_row, bias_l, cb_l) + 32 * u + 4 * g;
                     bias2[0] = *reinterpret_cast<const f32x4*>(bp);
                     bias2[1] = *reinterpret_cast<const f32x4*>(bp + 16);
                 } else {
@@ -306,38 +253,15 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
                     if (c < pd.nchunks) {
 #pragma unroll
                         for (int p2 = 0; p2 < 8; ++p2) {
-                            const int m = p2 & 3;       // pair inside the mini-chunk
-                            const int nx_slot = (rd_slot + 1 == CL_SNB) ? 0 : rd_slot + 1;
-                            const char* cbp = ring_ptr + rd_slot * CL_MINI + lane * 16;
-                            const char* nbp = ring_ptr + nx_slot * CL_MINI + lane * 16;
-                            if (m == 2) {
-                                // the next mini-chunk is about to be read: it has landed once only the two mini-chunks after it and the
-                                // two pieces issued so far in this one are still in flight (mlp_split_kernel.hip)
-                                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (CL_SNB - 3) + 2) : "memory");
-                            }
-                            if ((p2 & 1) == 0) {
-                                __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0), vmcnt / expcnt untouched
-                                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                                for (int q = 0; q < 2; ++q) {
-                                    const int sp = m + 2 + q;
-                                    abuf[(p2 + 2 + q) % 4] = (sp < 4) ? *reinterpret_cast<const f32x4*>(cbp + sp * 1024)
-                                                                      : *reinterpret_cast<const f32x4*>(nbp + (sp - 4) * 1024);
-                                }
-                            }
-                            const f32x4 av = abuf[p2 % 4];       // {tile 0, k-step 2 p2 | tile 1, 2 p2 | tile 0, 2 p2 + 1 | tile 1, 2 p2 + 1}
+                            ring.ahead(p2);                      // a ring step = a pair of k-steps of the wave's two row tiles
+                            const f32x4 av = ring.abuf[p2 % 4];  // {tile 0, k-step 2 p2 | tile 1, 2 p2 | tile 0, 2 p2 + 1 | tile 1, 2 p2 + 1}
                             const float b0 = sin_[16 * c + 2 * p2], b1 = sin_[16 * c + 2 * p2 + 1];
                             acc[0] = MFMA16(av.x, b0, (c == 0 && p2 == 0) ? bias2[0] : acc[0]);
-                            // refill of the slot behind the read pointer: one DMA piece per pair, behind an MFMA
-                            if (m == 0) { glds_set_dst(idst); glds_piece_m0<0>(isrc, lane_off, idst); };
-                            if (m == 1) glds_piece_m0<1>(isrc, lane_off, idst);
-                            if (m == 2) glds_piece_m0<2>(isrc, lane_off, idst);
-                            if (m == 3) { glds_piece_m0<3>(isrc, lane_off, idst); issue_next(); }
+                            ring.behind_first(p2);
                             acc[1] = MFMA16(av.y, b0, (c == 0 && p2 == 0) ? bias2[1] : acc[1]);
                             acc[0] = MFMA16(av.z, b1, acc[0]);
                             acc[1] = MFMA16(av.w, b1, acc[1]);
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (m == 3) rd_slot = nx_slot;
+                            ring.behind_last(p2);
                         }
                     }
                 }
@@ -352,7 +276,7 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            bits |= (own[j][r] > 0.f ? 1u : 0u) << (4 * j + r);
+                            bits |= mask_bit(own[j][r], 4 * j + r);
                             own[j][r] = relu1(own[j][r]);
                         }
                     mask_l[pd.mask_slot * 256 + tid] = (unsigned short)bits;
@@ -386,18 +310,7 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
                 // final layer (512 -> 1) + tanh, redundantly in every wave; then the backward seed -- for ALL rows, locally: the relu output
                 // of the last hidden layer is positive exactly where its mask bit is set
                 const float* wl = bias_l + a.wlast_row * WIDTH + 4 * g;
-                float part = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + 16 * t);
-                    part = fmaf(sin_[4 * t + 0], w4.x, part);
-                    part = fmaf(sin_[4 * t + 1], w4.y, part);
-                    part = fmaf(sin_[4 * t + 2], w4.z, part);
-                    part = fmaf(sin_[4 * t + 3], w4.w, part);
-                }
-                part += __shfl_xor(part, 16);
-                part += __shfl_xor(part, 32);
-                y = tanhf(part + a.b_last);
+                y = final_layer_sdf(a, bias_l, g, sin_);
                 const float d = 1.f - y * y;
 #pragma unroll
                 for (int t = 0; t < 32; ++t) {
@@ -420,30 +333,15 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
         if (u == 0) {
             const int n_code_tiles = 31 - a.lat_tile;              // 4 (64-D codes) or 2 (32-D)
             const f32x4 sx = xch[a.lat_tile * 64 + lane];           // the xyz tile: rows 13..15 = lane group 3, components 1..3
-            float* orow = a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE;
-            if (valid) {
+            float skipc[16];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if (t < n_code_tiles) sc = xch[(a.lat_tile + 1 + t) * 64 + lane];
-                    float4 o4;
-                    o4.x = sin_[4 * t + 0] + sc.x;
-                    o4.y = sin_[4 * t + 1] + sc.y;
-                    o4.z = sin_[4 * t + 2] + sc.z;
-                    o4.w = sin_[4 * t + 3] + sc.w;
-                    *reinterpret_cast<float4*>(orow + 16 * t + 4 * g) = o4;
-                }
+            for (int t = 0; t < 4; ++t) {
+                f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (t < n_code_tiles) sc = xch[(a.lat_tile + 1 + t) * 64 + lane];
+                skipc[4 * t + 0] = sc.x; skipc[4 * t + 1] = sc.y; skipc[4 * t + 2] = sc.z; skipc[4 * t + 3] = sc.w;
             }
-            const float s0 = __shfl(sx.y, pl + 48);
-            const float s1 = __shfl(sx.z, pl + 48);
-            const float s2 = __shfl(sx.w, pl + 48);
-            const float sk = (g == 0) ? s0 : (g == 1) ? s1 : s2;
-            if (valid) orow[64 + g] = (g < 3) ? (gfirst + sk) : y;
-            if (launch_ok && a.sdf_scatter && tile >= (a.direct.kind ? dl.nt0 : *a.scatter_tile_begin)) {
-                const bool sc = valid && g == 3;
-                if (a.guard) prepass_guard(a, td.z, sc, sc ? a.sdf_scatter[__float_as_int(pt.w)] : 1.0f, y);
-                if (sc) a.sdf_scatter[__float_as_int(pt.w)] = y;
-            }
+            write_jgrad_row(a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE, valid, g, pl, sin_, skipc, sx.y, sx.z, sx.w, gfirst, y);
+            if (launch_ok && a.sdf_scatter && tile >= (a.direct.kind ? dl.nt0 : *a.scatter_tile_begin)) scatter_sdf(a, td.z, valid && g == 3, pt, y);
         }
         // stores and LDS-DMA share vmcnt and may retire out of order: drain before counting again
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -451,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void mlp_cluster_kernel(const MlpArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-size_t mlp_cluster_lds_bytes() { return BIAS_BYTES + CODEBIAS_BYTES + CL_MASK_BYTES + CL_XCH_BYTES + CL_RING_BYTES; }
+size_t mlp_cluster_lds_bytes() { return LDS_HEAD_BYTES + CL_MASK_BYTES + CL_XCH_BYTES + CL_RING_BYTES; }
 
 hipError_t mlp_cluster_prepare_device() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_cluster_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_cluster_lds_bytes());

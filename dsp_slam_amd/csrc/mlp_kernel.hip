@@ -1,8 +1,8 @@
 // DeepSDF decoder forward / forward+input-gradient for gfx950 (MI355X), fp32 MFMA.
 //
 // Replaces, for batches of object-frame points:
-//   decode_sdf              reconstruct/loss_utils.py:51-79   (mlp_kernel<false>)
-//   get_batch_sdf_jacobian  reconstruct/loss_utils.py:82-103  (mlp_kernel<true>)
+//   decode_sdf              reconstruct/loss_utils.py:51-79   (mlp_kernel<0 / 1>)
+//   get_batch_sdf_jacobian  reconstruct/loss_utils.py:82-103  (mlp_kernel<2>, <3>)
 //   Decoder.forward         deep_sdf/deep_sdf_decoder.py:75-110
 //
 // Design (DESIGN.md "K1/K2"):  one workgroup = 4 waves = one 64-point tile, one wave per SIMD with the
@@ -17,12 +17,6 @@
 #include "mlp_common.h"
 
 namespace dsp {
-
-// relu-mask bit of one pre-activation, shifted into `bits` (bits = 2 * bits + (x > 0)): v_cmp + v_addc instead of the
-// v_cmp / v_cndmask / v_lshl_or chain hipcc emits for `bits |= (x > 0) << k`.  Feed elements 15 down to 0 and element k ends at bit k.
-__device__ __forceinline__ void push_mask_bit(unsigned& bits, float x) {
-    asm volatile("v_cmp_lt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bits) : "v"(x) : "vcc");
-}
 
 #define FOR16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 
@@ -42,19 +36,18 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
     const int g = lane >> 4;    // MFMA k index of this lane group == 4-row block inside a 16-row tile
     const int pl = lane & 15;   // point of this lane inside the wave
 
-    float* bias_l = reinterpret_cast<float*>(smem);
-    float* cb_l = reinterpret_cast<float*>(smem + BIAS_BYTES);   // [0..511] layer-0 code bias, [512..1023] latent_in code bias
-    unsigned short* mask_l = reinterpret_cast<unsigned short*>(smem + BIAS_BYTES + CODEBIAS_BYTES);
-    char* ring_ptr = smem + BIAS_BYTES + CODEBIAS_BYTES + (MASKS ? MASK_BYTES : 0);
+    const DecoderLds lds = carve_lds(smem);
+    float* const bias_l = lds.bias;
+    float* const cb_l = lds.cb;
+    unsigned short* const mask_l = lds.mask;
+    char* ring_ptr = smem + LDS_HEAD_BYTES + (MASKS ? MASK_BYTES : 0);
     const unsigned ring0 = lds_addr(ring_ptr);
 
     const int n_tiles = *a.n_tiles;
     const int tile0 = a.tile_begin ? *a.tile_begin : 0;
     if (tile0 + (int)blockIdx.x >= n_tiles) return;
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[0] = clock64(); a.clk[1] = wall_clock64(); }
-    for (int i = tid; i < a.n_bias_rows * WIDTH; i += 256) bias_l[i] = a.bias_tab[i];
-    __syncthreads();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_bias_table(a, bias_l, tid);
 
     // ---- weight stream state (all wave-uniform) ---------------------------------------------------
     int issue_pos = 0, issue_slot = 0, rd_slot = 0;
@@ -107,26 +100,17 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
             guard_tol = 0.5f * __uint_as_float(a.guard[(size_t)td.z * a.guard_stride]);     // tile-uniform: the object's margin / 2
         }
         if (!valid) pt = make_float4(0.f, 0.f, 0.f, 0.f);
-        // The shape code is the same for every point of the tile, so its contribution to layer 0 and to the latent_in
-        // layer is a per-object bias vector (k_code_bias): stage both into LDS.  What is left of layer 0 is three
-        // multiply-adds per row (W0[:, xyz] . p) -- done on the VALU below instead of 16 mostly-empty MFMA chunks.
         if (DOFWD) {
-        reinterpret_cast<float4*>(cb_l)[tid] = reinterpret_cast<const float4*>(a.code_bias + (size_t)td.z * a.code_bias_stride)[tid];
-        __syncthreads();
-        {
-            const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
+            stage_code_bias(a, cb_l, td.z, tid);
+            __syncthreads();
 #pragma unroll
             for (int o = 0; o < 8; ++o) {
                 float pre[16];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int row = 16 * (4 * o + j);
-                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cb_l + row + 4 * g);
-                    const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + row);
-                    const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + row);
-                    const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + row);
+                    const f32x4 p4 = layer0_rows(a, bias_l, cb_l, g, 16 * (4 * o + j), pt);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pre[4 * j + r] = fmaf(wz[r], pt.z, fmaf(wy[r], pt.y, fmaf(wx[r], pt.x, c0[r])));
+                    for (int r = 0; r < 4; ++r) pre[4 * j + r] = p4[r];
                 }
                 if (MASKS) {
                     unsigned bits = 0;
@@ -138,7 +122,6 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
                 for (int k = 0; k < 16; ++k) sin_[16 * o + k] = relu1(pre[k]);
             }
         }
-        }
         float skipc[16];
         float skipx[3];
         float y = 0.f;
@@ -147,20 +130,17 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
         for (int i = 0; i < 16; ++i) skipc[i] = 0.f;
         skipx[0] = skipx[1] = skipx[2] = 0.f;
 
-        // seed of the backward sweep: d tanh * W_last, masked by the last hidden layer's relu
+        // seed of the backward sweep, all rows, from the relu masks of slot `slot`
         auto seed_backward = [&](int slot) {
-            const float* wl = bias_l + a.wlast_row * WIDTH + 4 * g;
             const float d = 1.f - y * y;
 #pragma unroll
             for (int o = 0; o < 8; ++o) {
                 const unsigned bits = mask_l[(slot * 8 + o) * 256 + tid];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + 16 * (4 * o + j));
-                    sin_[16 * o + 4 * j + 0] = ((bits >> (4 * j + 0)) & 1u) ? d * w4.x : 0.f;
-                    sin_[16 * o + 4 * j + 1] = ((bits >> (4 * j + 1)) & 1u) ? d * w4.y : 0.f;
-                    sin_[16 * o + 4 * j + 2] = ((bits >> (4 * j + 2)) & 1u) ? d * w4.z : 0.f;
-                    sin_[16 * o + 4 * j + 3] = ((bits >> (4 * j + 3)) & 1u) ? d * w4.w : 0.f;
+                    const f32x4 s4 = backward_seed_rows(a, bias_l, g, 4 * o + j, bits >> (4 * j), d);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sin_[16 * o + 4 * j + r] = s4[r];
                 }
             }
         };
@@ -168,17 +148,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
             // masks and sdf of this point as the forward (MODE 1) launch of the same iteration exported them; each lane
             // only ever touches its own 64 mask words, so no barrier is needed
             const int sidx = __float_as_int(pt.w);
-            const uint4* mp = reinterpret_cast<const uint4*>(a.mask_buf + ((size_t)sidx * 4 + g) * 64);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const uint4 w = valid ? mp[q] : make_uint4(0, 0, 0, 0);
-                const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    mask_l[(8 * q + 2 * e + 0) * 256 + tid] = (unsigned short)(ww[e] & 0xffffu);
-                    mask_l[(8 * q + 2 * e + 1) * 256 + tid] = (unsigned short)(ww[e] >> 16);
-                }
-            }
+            import_masks<8>(mask_words(a, sidx, g), valid, mask_l, tid);
             y = valid ? a.sdf_in[sidx] : 0.f;
             seed_backward(a.seed_slot);
         }
@@ -186,35 +156,8 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
         for (int ps = 0; ps < a.n_pass; ++ps) {
             const PassDesc pd = a.pass[ps];
             // ---- pass prologue ------------------------------------------------------------------------------------
-            if (pd.kind == 2) {
-                // latent_in layer: xyz re-enters at rows 445..447 (lane group 3); the code part is in the bias (cb_l + 512)
-                // (row 445 = tile 27, row 477 = tile 29 with 32-D codes; both are row 13 of their tile: lane group 3, registers 1..3)
-                if (g == 3) {
-                    if (a.lat_tile == 29) { sin_[117] = pt.x; sin_[118] = pt.y; sin_[119] = pt.z; }
-                    else { sin_[109] = pt.x; sin_[110] = pt.y; sin_[111] = pt.z; }
-                }
-            } else if (BWD && pd.kind == 5) {
-                // first layer, backward: d y / d xyz = W0[:, xyz]^T ga0 on the VALU (ga0 = the input slab of this pass,
-                // which the pass epilogue overwrites); the MFMA pass itself only produces the 64 code rows
-                const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
-                float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + 16 * t);
-                    const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + 16 * t);
-                    const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + 16 * t);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        gx = fmaf(wx[r], sin_[4 * t + r], gx);
-                        gy = fmaf(wy[r], sin_[4 * t + r], gy);
-                        gz = fmaf(wz[r], sin_[4 * t + r], gz);
-                    }
-                }
-                gx += __shfl_xor(gx, 16); gx += __shfl_xor(gx, 32);
-                gy += __shfl_xor(gy, 16); gy += __shfl_xor(gy, 32);
-                gz += __shfl_xor(gz, 16); gz += __shfl_xor(gz, 32);
-                gfirst = (g == 0) ? gx : (g == 1) ? gy : gz;
-            }
+            if (pd.kind == 2) reinject_xyz(sin_, g, a.lat_tile, pt);
+            else if (BWD && pd.kind == 5) gfirst = first_layer_xyz_grad(a, bias_l, g, sin_);
 
             // All 32 output tiles of the layer are MFMA accumulators (acc[4*og+j], 128 AGPRs) with static indices: the
             // group / chunk / k-step loops are fully unrolled and skipped by uniform branches, so no register is ever
@@ -224,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
                 if (og < pd.nog) {
                     f32x4 bias4[4];
                     if (pd.bias_row != -1) {
-                        const float* bp = (pd.bias_row == -2 ? cb_l + WIDTH : bias_l + pd.bias_row * WIDTH) + 64 * og + 4 * g;
+                        const float* bp = pass_bias_vec(pd.bias_row, bias_l, cb_l) + 64 * og + 4 * g;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) bias4[j] = *reinterpret_cast<const f32x4*>(bp + 16 * j);
                     } else {
@@ -300,21 +243,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
 #pragma unroll
                         for (int k = 0; k < 16; ++k) v[k] = relu1(v[k]);
                     } else if (BWD && pd.mask_slot >= 0) {
-                        if (pd.kind == 4) {
-                            // latent_in layer: rows 445..447 / 448..511 of its input are the re-injected xyz / code, not
-                            // relu outputs -- keep their gradients (unmasked) for the final d/d[code,xyz] sum
-                            if (a.lat_tile != 29) {          // 64-D codes: xyz at rows 445..447, code at 448..511
-                                if (og == 6) { skipx[0] = v[13]; skipx[1] = v[14]; skipx[2] = v[15]; }
-                                if (og == 7) {
-#pragma unroll
-                                    for (int k = 0; k < 16; ++k) skipc[k] = v[k];
-                                }
-                            } else if (og == 7) {            // 32-D codes: xyz at rows 477..479, code at 480..511 (code index 16 (j - 2) + 4 g + r)
-                                skipx[0] = v[5]; skipx[1] = v[6]; skipx[2] = v[7];
-#pragma unroll
-                                for (int k = 0; k < 8; ++k) skipc[k] = v[8 + k];
-                            }
-                        }
+                        if (pd.kind == 4) capture_skip_rows(a.lat_tile, og, v, skipx, skipc);
                         const unsigned bits = mask_l[(pd.mask_slot * 8 + og) * 256 + tid];
 #pragma unroll
                         for (int k = 0; k < 16; ++k) v[k] = ((bits >> k) & 1u) ? v[k] : 0.f;
@@ -325,35 +254,14 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
             }
 
             if (DOFWD && ps == a.n_fwd - 1) {
-                // final layer (512 -> 1) on the VALU + tanh  (deep_sdf_decoder.py:93,107-108)
-                const float* wl = bias_l + a.wlast_row * WIDTH + 4 * g;
-                float part = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + 16 * t);
-                    part = fmaf(sin_[4 * t + 0], w4.x, part);
-                    part = fmaf(sin_[4 * t + 1], w4.y, part);
-                    part = fmaf(sin_[4 * t + 2], w4.z, part);
-                    part = fmaf(sin_[4 * t + 3], w4.w, part);
-                }
-                part += __shfl_xor(part, 16);
-                part += __shfl_xor(part, 32);
-                y = tanhf(part + a.b_last);
+                y = final_layer_sdf(a, bias_l, g, sin_);
                 if (!BWD) {
                     if (a.guard) prepass_guard_tol(a, td.z, valid && g == 0, old_lp, y, guard_tol);
                     if (valid && g == 0) a.out_sdf[a.index ? src : pidx + td.w] = y;
                     if (MODE == 1 && valid && y > -a.th && y < a.th) {
                         // a candidate row of the render term (loss.py:88): export this lane's 64 mask words (8 layers x 8
                         // output groups) so that the jacobian launch can run the backward sweep without a second forward
-                        uint4* mp = reinterpret_cast<uint4*>(a.mask_buf + ((size_t)src * 4 + g) * 64);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            unsigned ww[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                ww[e] = (unsigned)mask_l[(8 * q + 2 * e + 0) * 256 + tid] | ((unsigned)mask_l[(8 * q + 2 * e + 1) * 256 + tid] << 16);
-                            mp[q] = make_uint4(ww[0], ww[1], ww[2], ww[3]);
-                        }
+                        export_masks<8>(mask_words(a, src, g), mask_l, tid);
                     }
                 } else {
                     seed_backward(pd.mask_slot);
@@ -363,28 +271,8 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
 
         if (BWD) {
             // sin_[0..15] now holds d y / d code through the first layer (rows 16t + 4g + r); gfirst the xyz part
-            float* orow = a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE;
-            if (valid) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float4 o4;
-                    o4.x = sin_[4 * t + 0] + skipc[4 * t + 0];
-                    o4.y = sin_[4 * t + 1] + skipc[4 * t + 1];
-                    o4.z = sin_[4 * t + 2] + skipc[4 * t + 2];
-                    o4.w = sin_[4 * t + 3] + skipc[4 * t + 3];
-                    *reinterpret_cast<float4*>(orow + 16 * t + 4 * g) = o4;
-                }
-            }
-            const float s0 = __shfl(skipx[0], pl + 48);
-            const float s1 = __shfl(skipx[1], pl + 48);
-            const float s2 = __shfl(skipx[2], pl + 48);
-            const float sk = (g == 0) ? s0 : (g == 1) ? s1 : s2;
-            if (valid) orow[64 + g] = (g < 3) ? (gfirst + sk) : y;
-            if (MODE == 2 && a.sdf_scatter && tile >= *a.scatter_tile_begin) {
-                const bool sc = valid && g == 3;
-                if (a.guard) prepass_guard(a, td.z, sc, sc ? a.sdf_scatter[__float_as_int(pt.w)] : 1.0f, y);
-                if (sc) a.sdf_scatter[__float_as_int(pt.w)] = y;
-            }
+            write_jgrad_row(a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE, valid, g, pl, sin_, skipc, skipx[0], skipx[1], skipx[2], gfirst, y);
+            if (MODE == 2 && a.sdf_scatter && tile >= *a.scatter_tile_begin) scatter_sdf(a, td.z, valid && g == 3, pt, y);
         }
         // stores and LDS-DMA share vmcnt and may retire out of order: drain before counting again
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -393,33 +281,21 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[2] = clock64(); a.clk[3] = wall_clock64(); }
 }
 
-template __global__ void mlp_kernel<0>(const MlpArgs);
-template __global__ void mlp_kernel<1>(const MlpArgs);
-template __global__ void mlp_kernel<2>(const MlpArgs);
-template __global__ void mlp_kernel<3>(const MlpArgs);
+static void (*const MLP_KERNELS[4])(const MlpArgs) = {mlp_kernel<0>, mlp_kernel<1>, mlp_kernel<2>, mlp_kernel<3>};     // [MODE]
 
-size_t mlp_lds_bytes(int mode) { return BIAS_BYTES + CODEBIAS_BYTES + (mode != 0 ? MASK_BYTES : 0) + NBUF * CHUNK_BYTES; }
+size_t mlp_lds_bytes(int mode) { return LDS_HEAD_BYTES + (mode != 0 ? MASK_BYTES : 0) + NBUF * CHUNK_BYTES; }
 
 // Opt every kernel variant into > 64 KiB of dynamic LDS on the current device (called by dsp_create).
 hipError_t mlp_prepare_device() {
-    const void* fns[4] = {reinterpret_cast<const void*>(&mlp_kernel<0>), reinterpret_cast<const void*>(&mlp_kernel<1>),
-                          reinterpret_cast<const void*>(&mlp_kernel<2>), reinterpret_cast<const void*>(&mlp_kernel<3>)};
     for (int i = 0; i < 4; ++i) {
-        const hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_lds_bytes(i));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(MLP_KERNELS[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_lds_bytes(i));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
 hipError_t launch_mlp(int mode, const MlpArgs& args, int n_blocks, hipStream_t stream) {
-    if (mode == 0)
-        hipLaunchKernelGGL((mlp_kernel<0>), dim3(n_blocks), dim3(256), mlp_lds_bytes(0), stream, args);
-    else if (mode == 1)
-        hipLaunchKernelGGL((mlp_kernel<1>), dim3(n_blocks), dim3(256), mlp_lds_bytes(1), stream, args);
-    else if (mode == 2)
-        hipLaunchKernelGGL((mlp_kernel<2>), dim3(n_blocks), dim3(256), mlp_lds_bytes(2), stream, args);
-    else
-        hipLaunchKernelGGL((mlp_kernel<3>), dim3(n_blocks), dim3(256), mlp_lds_bytes(3), stream, args);
+    hipLaunchKernelGGL(MLP_KERNELS[mode], dim3(n_blocks), dim3(256), mlp_lds_bytes(mode), stream, args);
     return hipGetLastError();
 }
 

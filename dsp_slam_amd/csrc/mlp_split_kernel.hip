@@ -7,10 +7,11 @@
 // the OUTPUT ROWS of every layer instead: wave w produces output groups 2w and 2w+1 (128 rows = 8 MFMA tiles, 1024 MFMAs
 // per pass), and the layer's [512 x 16] result is exchanged through LDS (32 KiB, two barriers per layer) so that every
 // wave again holds the full input slab of the next layer in registers.  Same k order, same bias seeding, same masks per
-// output element as mlp_kernel<2>, hence bit-identical gradients (tests/test_gpu_configs.py::test_split_kernel_is_exact).
+// output element as mlp_kernel<2> -- the tile steps are the same code (mlp_common.h) -- hence bit-identical gradients
+// (tests/test_gpu_configs.py::test_split_kernel_is_exact).
 //
-// Weights: waves no longer share A operands, so each wave streams its own rows through a private LDS ring (5 mini-chunks
-// of 4 k-steps = 4 KiB; one LDS-DMA piece per k-step, counted vmcnt, no barrier).  The host lays a second copy of the
+// Weights: waves no longer share A operands, so each wave streams its own rows through a private LDS ring (WaveRing, mlp_common.h:
+// 5 mini-chunks of 4 k-steps = 4 KiB; one LDS-DMA piece per k-step, counted vmcnt, no barrier).  The host lays a second copy of the
 // weight stream out per wave (`wsplit`: for each pass, the chunks of the wave's two output groups in consumption order),
 // so the stream position is a single wrapping pointer per wave.
 //
@@ -46,12 +47,11 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
     const int g = lane >> 4;
     const int pl = lane & 15;
 
-    float* bias_l = reinterpret_cast<float*>(smem);
-    float* cb_l = reinterpret_cast<float*>(smem + BIAS_BYTES);
-    unsigned short* mask_l = reinterpret_cast<unsigned short*>(smem + BIAS_BYTES + CODEBIAS_BYTES);
-    f32x4* xch = reinterpret_cast<f32x4*>(smem + BIAS_BYTES + CODEBIAS_BYTES + SPLIT_MASK_BYTES);
-    char* ring_ptr = smem + BIAS_BYTES + CODEBIAS_BYTES + SPLIT_MASK_BYTES + XCH_BYTES + wave * (SNB * MINI_BYTES);
-    const unsigned ring0 = lds_addr(ring_ptr);
+    const DecoderLds lds = carve_lds(smem);
+    float* const bias_l = lds.bias;
+    float* const cb_l = lds.cb;
+    unsigned short* const mask_l = lds.mask;
+    f32x4* xch = reinterpret_cast<f32x4*>(smem + LDS_HEAD_BYTES + SPLIT_MASK_BYTES);
 
     DirectList dl{0, 0, 0, 0};
     if (a.direct.kind) dl = direct_list(a.direct, SPLIT_TILE_PTS);
@@ -64,33 +64,18 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
     const bool counted = BWD && n_tiles < a.split_min_tiles && cl_err == (a.cl_epoch_base | 1u);
     if (a.direct.kind && blockIdx.x == 0 && tid == 0 && !counted) direct_commit(a.direct, dl);
     if ((int)blockIdx.x >= n_tiles) return;
-    for (int i = tid; i < a.n_bias_rows * WIDTH; i += 256) bias_l[i] = a.bias_tab[i];
-    __syncthreads();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_bias_table(a, bias_l, tid);
 
     // ---- this wave's weight stream (wave-uniform state) -----------------------------------------------------------------
     const int total_minis = (BWD ? a.split_len[wave] : a.split_len_fwd[wave]) * (CHUNK_BYTES / MINI_BYTES);
     const int fwd_minis = a.split_len_fwd[wave] * (CHUNK_BYTES / MINI_BYTES);
     const char* wbase = reinterpret_cast<const char*>(a.wsplit) + (size_t)a.split_off[wave] * CHUNK_BYTES;   // wave-uniform
-    const unsigned lane_off = lane * 16;
     // mixed launch: tiles from bo_begin on run the backward sweep only; the stream then starts (and wraps to) the backward part
     const int bo_begin = (BWD && a.bwd_only_tile_begin) ? *a.bwd_only_tile_begin : 0x7fffffff;
-    int wrap_to = (BWD && (int)blockIdx.x >= bo_begin) ? fwd_minis : 0;       // where the stream (re)starts: the kind of the NEXT tile to be fed
-    int issue_pos = wrap_to, issue_slot = 0, rd_slot = 0;
-    const char* isrc = wbase + (size_t)issue_pos * MINI_BYTES;
-    unsigned idst = ring0;
-    auto issue_next = [&]() {
-        issue_pos = (issue_pos + 1 == total_minis) ? wrap_to : issue_pos + 1;
-        issue_slot = (issue_slot + 1 == SNB) ? 0 : issue_slot + 1;
-        isrc = wbase + (size_t)issue_pos * MINI_BYTES;
-        idst = ring0 + issue_slot * MINI_BYTES;
-    };
-#pragma unroll
-    for (int i = 0; i < SNB - 1; ++i) { glds_quarter(isrc, lane_off, idst); issue_next(); }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (SNB - 2)) : "memory");     // mini-chunk 0 has landed
-    f32x4 abuf[4];
-    abuf[0] = *reinterpret_cast<const f32x4*>(ring_ptr + lane * 16);
-    abuf[1] = *reinterpret_cast<const f32x4*>(ring_ptr + lane * 16 + 1024);
+    WaveRing<SNB, MINI_BYTES> ring;
+    // where the stream (re)starts: the kind of the NEXT tile to be fed
+    ring.prime(wbase, smem + LDS_HEAD_BYTES + SPLIT_MASK_BYTES + XCH_BYTES + wave * (SNB * MINI_BYTES), lane, total_minis,
+               (BWD && (int)blockIdx.x >= bo_begin) ? fwd_minis : 0);
 
     float sin_[128];   // full input slab of the current pass (every wave holds all 512 rows of the 16 points)
     f32x4 acc[8];      // this wave's two output groups
@@ -98,9 +83,6 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
     for (int i = 0; i < 128; ++i) sin_[i] = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. the weight prefetch in flight
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     // own rows -> LDS, all rows <- LDS.  `nog` output groups of the layer are live; the others keep their old registers.
     auto exchange = [&](const float (&own)[2][16], int nog) {
@@ -136,41 +118,28 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
         float4 pt = a.pts[src];
         if (!valid) pt = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool bo = BWD && tile >= bo_begin;                                   // backward sweep only, from exported masks (workgroup-uniform)
-        if (BWD) wrap_to = ((int)(tile + gridDim.x) >= bo_begin) ? fwd_minis : 0;  // the prefetch wraps during this tile: to where the NEXT tile starts
+        if (BWD) ring.wrap_to = ((int)(tile + gridDim.x) >= bo_begin) ? fwd_minis : 0;  // the prefetch wraps during this tile: to where the NEXT tile starts
         lds_barrier();        // previous tile's readers of cb_l are done
-        reinterpret_cast<float4*>(cb_l)[tid] = reinterpret_cast<const float4*>(a.code_bias + (size_t)td.z * a.code_bias_stride)[tid];
+        stage_code_bias(a, cb_l, td.z, tid);
         lds_barrier();
         float y = 0.f;
         if (bo) {
             // masks and sdf of this point as the forward (MODE 1 / mlp_kernel<1>) launch of the same iteration exported them: this lane's words
-            // of the wave's two output groups for the eight mask slots.  Layout [sample][lane group][slot 8][group 8] u16; as u32 words,
-            // word 4 slot + w holds groups 2w (low half) and 2w + 1.
+            // of the wave's two output groups (word `wave` of each slot) for the eight mask slots
             const int sidx = __float_as_int(pt.w);
-            const unsigned* mp = reinterpret_cast<const unsigned*>(a.mask_buf + ((size_t)sidx * 4 + g) * 64) + wave;
-#pragma unroll
-            for (int sl = 0; sl < MASK_SLOTS; ++sl) {
-                const unsigned w = valid ? mp[4 * sl] : 0u;
-                mask_l[(sl * 2 + 0) * 256 + tid] = (unsigned short)(w & 0xffffu);
-                mask_l[(sl * 2 + 1) * 256 + tid] = (unsigned short)(w >> 16);
-            }
+            import_masks<2>(mask_words(a, sidx, g) + wave, valid, mask_l, tid);
             y = valid ? a.sdf_in[sidx] : 0.f;
         } else {   // layer 0 on the VALU, redundantly in every wave (the slab is needed everywhere); masks of the own groups only
-            const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
 #pragma unroll
             for (int o = 0; o < 8; ++o) {
                 unsigned bits = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int row = 16 * (4 * o + j);
-                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cb_l + row + 4 * g);
-                    const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + row);
-                    const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + row);
-                    const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + row);
+                    const f32x4 pre = layer0_rows(a, bias_l, cb_l, g, 16 * (4 * o + j), pt);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float pre = fmaf(wz[r], pt.z, fmaf(wy[r], pt.y, fmaf(wx[r], pt.x, c0[r])));
-                        bits |= (pre > 0.f ? 1u : 0u) << (4 * j + r);
-                        sin_[16 * o + 4 * j + r] = relu1(pre);
+                        bits |= mask_bit(pre[r], 4 * j + r);
+                        sin_[16 * o + 4 * j + r] = relu1(pre[r]);
                     }
                 }
                 if (MASKS && (o >> 1) == wave) mask_l[(0 * 2 + (o & 1)) * 256 + tid] = (unsigned short)bits;
@@ -183,9 +152,8 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
         for (int i = 0; i < 16; ++i) skipc[i] = 0.f;
         skipx[0] = skipx[1] = skipx[2] = 0.f;
 
-        // seed of the backward sweep on the own rows: d tanh * W_last, masked by the last hidden layer's relu (mask slot `slot`); then round the workgroup
+        // seed of the backward sweep on the own rows, from the relu masks of slot `slot`; then round the workgroup
         auto seed_backward = [&](int slot) {
-            const float* wl = bias_l + a.wlast_row * WIDTH + 4 * g;
             const float d = 1.f - y * y;
             float seed[2][16];
 #pragma unroll
@@ -194,11 +162,9 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
                 const unsigned bits = mask_l[(slot * 2 + ol) * 256 + tid];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + 16 * (4 * og + j));
-                    seed[ol][4 * j + 0] = ((bits >> (4 * j + 0)) & 1u) ? d * w4.x : 0.f;
-                    seed[ol][4 * j + 1] = ((bits >> (4 * j + 1)) & 1u) ? d * w4.y : 0.f;
-                    seed[ol][4 * j + 2] = ((bits >> (4 * j + 2)) & 1u) ? d * w4.z : 0.f;
-                    seed[ol][4 * j + 3] = ((bits >> (4 * j + 3)) & 1u) ? d * w4.w : 0.f;
+                    const f32x4 s4 = backward_seed_rows(a, bias_l, g, 4 * og + j, bits >> (4 * j), d);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) seed[ol][4 * j + r] = s4[r];
                 }
             }
             exchange(seed, 8);
@@ -207,32 +173,8 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
 
         for (int ps = bo ? a.n_fwd : 0; ps < a.n_pass; ++ps) {
             const PassDesc pd = a.pass[ps];
-            if (pd.kind == 2) {
-                // (row 445 = tile 27, row 477 = tile 29 with 32-D codes; both are row 13 of their tile: lane group 3, registers 1..3)
-                if (g == 3) {
-                    if (a.lat_tile == 29) { sin_[117] = pt.x; sin_[118] = pt.y; sin_[119] = pt.z; }
-                    else { sin_[109] = pt.x; sin_[110] = pt.y; sin_[111] = pt.z; }
-                }
-            } else if (BWD && pd.kind == 5) {
-                const float* w0 = bias_l + a.w0_row * WIDTH + 4 * g;
-                float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 wx = *reinterpret_cast<const f32x4*>(w0 + 16 * t);
-                    const f32x4 wy = *reinterpret_cast<const f32x4*>(w0 + WIDTH + 16 * t);
-                    const f32x4 wz = *reinterpret_cast<const f32x4*>(w0 + 2 * WIDTH + 16 * t);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        gx = fmaf(wx[r], sin_[4 * t + r], gx);
-                        gy = fmaf(wy[r], sin_[4 * t + r], gy);
-                        gz = fmaf(wz[r], sin_[4 * t + r], gz);
-                    }
-                }
-                gx += __shfl_xor(gx, 16); gx += __shfl_xor(gx, 32);
-                gy += __shfl_xor(gy, 16); gy += __shfl_xor(gy, 32);
-                gz += __shfl_xor(gz, 16); gz += __shfl_xor(gz, 32);
-                gfirst = (g == 0) ? gx : (g == 1) ? gy : gz;
-            }
+            if (pd.kind == 2) reinject_xyz(sin_, g, a.lat_tile, pt);
+            else if (BWD && pd.kind == 5) gfirst = first_layer_xyz_grad(a, bias_l, g, sin_);
 
             // ---- this wave's two output groups: 2 x nchunks x 16 k-steps, statically indexed accumulators -------------------
 #pragma unroll
@@ -241,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
                 if (og < pd.nog) {
                     f32x4 bias4[4];
                     if (pd.bias_row != -1) {
-                        const float* bp = (pd.bias_row == -2 ? cb_l + WIDTH : bias_l + pd.bias_row * WIDTH) + 64 * og + 4 * g;
+                        const float* bp = pass_bias_vec(pd.bias_row, bias_l, cb_l) + 64 * og + 4 * g;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) bias4[j] = *reinterpret_cast<const f32x4*>(bp + 16 * j);
                     } else {
@@ -253,41 +195,15 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
                         if (c < pd.nchunks) {
 #pragma unroll
                             for (int s = 0; s < KSTEPS_PER_CHUNK; ++s) {
-                                const int m = s & 3;       // k-step inside the mini-chunk
-                                const int nx_slot = (rd_slot + 1 == SNB) ? 0 : rd_slot + 1;
-                                const char* cbp = ring_ptr + rd_slot * MINI_BYTES + lane * 16;
-                                const char* nbp = ring_ptr + nx_slot * MINI_BYTES + lane * 16;
-                                if (m == 2) {
-                                    // the next mini-chunk is about to be read: it has landed once only the two mini-chunks
-                                    // after it and the two pieces issued so far in this one are still in flight
-                                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (SNB - 3) + 2) : "memory");
-                                }
-                                static_assert(PAIR_READS == 2, "pairs");
-                                // A operands in pairs, one lgkmcnt wait per pair (mlp_common.h): at m == 2 the pair belongs to the next
-                                // mini-chunk, which the vmcnt wait above has just proven landed
-                                if ((s & 1) == 0) {
-                                    __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0), vmcnt / expcnt untouched
-                                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                                    for (int q = 0; q < 2; ++q) {
-                                        const int sp = m + 2 + q;
-                                        abuf[(s + 2 + q) % 4] = (sp < 4) ? *reinterpret_cast<const f32x4*>(cbp + sp * 1024)
-                                                                         : *reinterpret_cast<const f32x4*>(nbp + (sp - 4) * 1024);
-                                    }
-                                }
-                                const f32x4 av = abuf[s % 4];
+                                ring.ahead(s);                   // a ring step = one k-step of the wave's four row tiles
+                                const f32x4 av = ring.abuf[s % 4];
                                 const float b = sin_[16 * c + s];
                                 acc[4 * ol + 0] = MFMA16(av.x, b, (c == 0 && s == 0) ? bias4[0] : acc[4 * ol + 0]);
-                                // refill of the slot behind the read pointer: one DMA piece per k-step, behind an MFMA
-                                if (m == 0) { glds_set_dst(idst); glds_piece_m0<0>(isrc, lane_off, idst); };
-                                if (m == 1) glds_piece_m0<1>(isrc, lane_off, idst);
-                                if (m == 2) glds_piece_m0<2>(isrc, lane_off, idst);
-                                if (m == 3) { glds_piece_m0<3>(isrc, lane_off, idst); issue_next(); }
+                                ring.behind_first(s);
                                 acc[4 * ol + 1] = MFMA16(av.y, b, (c == 0 && s == 0) ? bias4[1] : acc[4 * ol + 1]);
                                 acc[4 * ol + 2] = MFMA16(av.z, b, (c == 0 && s == 0) ? bias4[2] : acc[4 * ol + 2]);
                                 acc[4 * ol + 3] = MFMA16(av.w, b, (c == 0 && s == 0) ? bias4[3] : acc[4 * ol + 3]);
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (m == 3) rd_slot = nx_slot;
+                                ring.behind_last(s);
                             }
                         }
                     }
@@ -309,24 +225,12 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
                         unsigned bits = 0;
 #pragma unroll
                         for (int k = 0; k < 16; ++k) {
-                            bits |= (own[ol][k] > 0.f ? 1u : 0u) << k;
+                            bits |= mask_bit(own[ol][k], k);
                             own[ol][k] = relu1(own[ol][k]);
                         }
                         if (MASKS) mask_l[(pd.mask_slot * 2 + ol) * 256 + tid] = (unsigned short)bits;
                     } else if (BWD && pd.mask_slot >= 0) {
-                        if (pd.kind == 4) {      // latent_in layer: gradients of the re-injected xyz / code rows, unmasked (wave 3)
-                            if (a.lat_tile != 29) {          // 64-D codes: xyz at rows 445..447, code at 448..511
-                                if (og == 6) { skipx[0] = own[ol][13]; skipx[1] = own[ol][14]; skipx[2] = own[ol][15]; }
-                                if (og == 7) {
-#pragma unroll
-                                    for (int k = 0; k < 16; ++k) skipc[k] = own[ol][k];
-                                }
-                            } else if (og == 7) {            // 32-D codes: xyz at rows 477..479, code at 480..511 (code index 16 (j - 2) + 4 g + r)
-                                skipx[0] = own[ol][5]; skipx[1] = own[ol][6]; skipx[2] = own[ol][7];
-#pragma unroll
-                                for (int k = 0; k < 8; ++k) skipc[k] = own[ol][8 + k];
-                            }
-                        }
+                        if (pd.kind == 4) capture_skip_rows(a.lat_tile, og, own[ol], skipx, skipc);      // (groups 6, 7: wave 3)
                         const unsigned bits = mask_l[(pd.mask_slot * 2 + ol) * 256 + tid];
 #pragma unroll
                         for (int k = 0; k < 16; ++k) own[ol][k] = ((bits >> k) & 1u) ? own[ol][k] : 0.f;
@@ -337,19 +241,7 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
 
             if (ps == a.n_fwd - 1) {
                 // final layer (512 -> 1) + tanh, redundantly in every wave; then the backward seed on the own rows
-                const float* wl = bias_l + a.wlast_row * WIDTH + 4 * g;
-                float part = 0.f;
-#pragma unroll
-                for (int t = 0; t < 32; ++t) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + 16 * t);
-                    part = fmaf(sin_[4 * t + 0], w4.x, part);
-                    part = fmaf(sin_[4 * t + 1], w4.y, part);
-                    part = fmaf(sin_[4 * t + 2], w4.z, part);
-                    part = fmaf(sin_[4 * t + 3], w4.w, part);
-                }
-                part += __shfl_xor(part, 16);
-                part += __shfl_xor(part, 32);
-                y = tanhf(part + a.b_last);
+                y = final_layer_sdf(a, bias_l, g, sin_);
                 if (!BWD) {
                     if (wave == 0) {      // wave-uniform: the four waves of a tile hold the same 16 points
                         const bool st = g == 0 && valid;
@@ -359,10 +251,7 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
                     if (MODE == 1 && valid && y > -a.th && y < a.th) {
                         // a candidate row of the render term (loss.py:88): export this lane's mask words of the wave's two output groups,
                         // all eight slots, in mlp_kernel<1>'s layout -- the mixed jacobian launch runs this sample backward-only from them
-                        unsigned* mp = reinterpret_cast<unsigned*>(a.mask_buf + ((size_t)src * 4 + g) * 64) + wave;
-#pragma unroll
-                        for (int sl = 0; sl < MASK_SLOTS; ++sl)
-                            mp[4 * sl] = (unsigned)mask_l[(sl * 2 + 0) * 256 + tid] | ((unsigned)mask_l[(sl * 2 + 1) * 256 + tid] << 16);
+                        export_masks<2>(mask_words(a, src, g) + wave, mask_l, tid);
                     }
                     continue;
                 }
@@ -373,28 +262,8 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
         // d y / d code = first-layer rows (group 0, held by every wave after the last exchange) + the latent_in skip rows that
         // only wave 3 captured; it writes the row
         if (BWD && wave == 3) {
-            float* orow = a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE;
-            if (valid) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float4 o4;
-                    o4.x = sin_[4 * t + 0] + skipc[4 * t + 0];
-                    o4.y = sin_[4 * t + 1] + skipc[4 * t + 1];
-                    o4.z = sin_[4 * t + 2] + skipc[4 * t + 2];
-                    o4.w = sin_[4 * t + 3] + skipc[4 * t + 3];
-                    *reinterpret_cast<float4*>(orow + 16 * t + 4 * g) = o4;
-                }
-            }
-            const float s0 = __shfl(skipx[0], pl + 48);
-            const float s1 = __shfl(skipx[1], pl + 48);
-            const float s2 = __shfl(skipx[2], pl + 48);
-            const float sk = (g == 0) ? s0 : (g == 1) ? s1 : s2;
-            if (valid) orow[64 + g] = (g < 3) ? (gfirst + sk) : y;
-            if (a.sdf_scatter && tile >= (a.direct.kind ? dl.nt0 : *a.scatter_tile_begin)) {
-                const bool sc = valid && g == 3;
-                if (a.guard) prepass_guard(a, td.z, sc, sc ? a.sdf_scatter[__float_as_int(pt.w)] : 1.0f, y);
-                if (sc) a.sdf_scatter[__float_as_int(pt.w)] = y;
-            }
+            write_jgrad_row(a.out_grad + (size_t)(pidx + td.w) * GRAD_STRIDE, valid, g, pl, sin_, skipc, skipx[0], skipx[1], skipx[2], gfirst, y);
+            if (a.sdf_scatter && tile >= (a.direct.kind ? dl.nt0 : *a.scatter_tile_begin)) scatter_sdf(a, td.z, valid && g == 3, pt, y);
         }
         // stores and LDS-DMA share vmcnt and may retire out of order: drain before counting again
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -402,17 +271,13 @@ __global__ __launch_bounds__(256, 1) void mlp_split_kernel(const MlpArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-size_t mlp_split_lds_bytes() { return BIAS_BYTES + CODEBIAS_BYTES + SPLIT_MASK_BYTES + XCH_BYTES + SPLIT_RING_BYTES; }
+size_t mlp_split_lds_bytes() { return LDS_HEAD_BYTES + SPLIT_MASK_BYTES + XCH_BYTES + SPLIT_RING_BYTES; }
 
-template __global__ void mlp_split_kernel<0>(const MlpArgs);
-template __global__ void mlp_split_kernel<1>(const MlpArgs);
-template __global__ void mlp_split_kernel<2>(const MlpArgs);
+static void (*const SPLIT_KERNELS[3])(const MlpArgs) = {mlp_split_kernel<0>, mlp_split_kernel<1>, mlp_split_kernel<2>};     // [MODE]
 
 hipError_t mlp_split_prepare_device() {
-    const void* fns[3] = {reinterpret_cast<const void*>(&mlp_split_kernel<0>), reinterpret_cast<const void*>(&mlp_split_kernel<1>),
-                          reinterpret_cast<const void*>(&mlp_split_kernel<2>)};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_split_lds_bytes());
+    for (int i = 0; i < 3; ++i) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(SPLIT_KERNELS[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_split_lds_bytes());
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -420,12 +285,7 @@ hipError_t mlp_split_prepare_device() {
 
 // mode 0 forward, 1 forward + relu-mask export, 2 forward + backward (+ backward-only tiles from args.bwd_only_tile_begin on)
 hipError_t launch_mlp_split(int mode, const MlpArgs& args, int n_blocks, hipStream_t stream) {
-    if (mode == 2)
-        hipLaunchKernelGGL(mlp_split_kernel<2>, dim3(n_blocks), dim3(256), mlp_split_lds_bytes(), stream, args);
-    else if (mode == 1)
-        hipLaunchKernelGGL(mlp_split_kernel<1>, dim3(n_blocks), dim3(256), mlp_split_lds_bytes(), stream, args);
-    else
-        hipLaunchKernelGGL(mlp_split_kernel<0>, dim3(n_blocks), dim3(256), mlp_split_lds_bytes(), stream, args);
+    hipLaunchKernelGGL(SPLIT_KERNELS[mode], dim3(n_blocks), dim3(256), mlp_split_lds_bytes(), stream, args);
     return hipGetLastError();
 }
 

@@ -38,6 +38,34 @@ def _run_traced(eng, prm, objs, n_it, **setters):
     return out
 
 
+# The smallest lists at which the decoder forms can still disagree: a detection of 17 surface points and 8 background rays is a list of 2-3
+# 16-point tiles whose last tile has ONE valid point (in the cluster form most clusters return at entry and the hand-off runs with one
+# live cluster).  Seeds chosen so that the run ends with status 0 and K > 0 in every traced iteration on its decoder (asserted where used).
+TINY_SEED_64, TINY_SEED_32 = 7, 7
+P32 = dict(k1=10.0, k2=100.0, k3=2.5, k4=0.0, b1=0.2, b2=0.02, lr=1.0, s_damp=100.0)      # the 32-D fixture decoder's settings
+
+
+def _tiny(code_len=64):
+    if code_len == 32:
+        return synth.make_object(TINY_SEED_32, n_surface=17, n_background=8, code_len=32, half=synth.CHAIR_HALF)
+    return synth.make_object(TINY_SEED_64, n_surface=17, n_background=8)
+
+
+def _assert_not_degenerate(run, what):
+    assert run[0][3][0] == 0, (what, "status", int(run[0][3][0]))
+    assert all(int(t["K"][0]) > 0 for t in run[1]), (what, "K", [int(t["K"][0]) for t in run[1]])
+
+
+def _assert_tiny_cluster_is_exact(e, prm, det, what):
+    for prepass in (0, 1):
+        off = _run_traced(e, prm, [det], 2, prepass=prepass, cluster_tiles=0)
+        on = _run_traced(e, prm, [det], 2, prepass=prepass, cluster_tiles=1)
+        for r in (off, on):
+            _assert_not_degenerate(r, (what, prepass))
+        _assert_same_bits(off, on, np.array([0]), "%s, cluster vs latency form, prepass %d" % (what, prepass))
+        assert off[2]["n_cluster_tiles"] == 0 and on[2]["n_cluster_tiles"] > 0, (what, prepass, on[2]["n_cluster_tiles"])
+
+
 def _assert_same_bits(a, c, rows, what):
     for x, y in zip(a[0], c[0]):
         assert np.array_equal(x, y), what
@@ -314,7 +342,7 @@ def test_cluster_kernel_is_exact(eng, chairs32_decoder):
     L2 after every pass) against the latency form it replaces for detection-sized lists: every bit of every iteration -- with the prepass
     (speculative band rows: sdf scattered back, guard comparisons) and without (surface points + kept render rows), on the 64-D and on
     the 32-D decoder (skip rows at other tiles), repeated runs (the exchange counters advance from launch to launch), and a list too
-    long for it (three detections: > 128 tiles), which must take the latency form."""
+    long for it (three detections: > 128 tiles), which must take the latency form; and the smallest list, on both decoders (_tiny)."""
     n_it = 4
     prm = E.gn_params(num_iterations=n_it)
     det = synth.make_object(4242, n_surface=250, n_background=200)
@@ -347,12 +375,16 @@ def test_cluster_kernel_is_exact(eng, chairs32_decoder):
     # the 32-D decoder: xyz re-enters at tile 29, code gradient rows at tiles 30, 31
     e32 = E.Engine(chairs32_decoder.layers, chairs32_decoder.latent_in, chairs32_decoder.code_len, device=0)
     o32 = synth.make_object(21, n_surface=220, n_background=60, code_len=32, half=synth.CHAIR_HALF)
-    p32 = E.gn_params(k1=10.0, k2=100.0, k3=2.5, k4=0.0, b1=0.2, b2=0.02, lr=1.0, s_damp=100.0, num_iterations=n_it)
+    p32 = E.gn_params(num_iterations=n_it, **P32)
     off = _run_traced(e32, p32, [o32], n_it, cluster_tiles=0)
     on = _run_traced(e32, p32, [o32], n_it, cluster_tiles=1)
-    e32.close()
-    _assert_same_bits(off, on, np.array([0]), "32-D decoder")
-    assert on[2]["n_cluster_tiles"] > 0
+    try:
+        _assert_same_bits(off, on, np.array([0]), "32-D decoder")
+        assert on[2]["n_cluster_tiles"] > 0
+        _assert_tiny_cluster_is_exact(e32, E.gn_params(num_iterations=2, **P32), _tiny(32), "tiny detection, 32-D decoder")
+    finally:
+        e32.close()
+    _assert_tiny_cluster_is_exact(eng, E.gn_params(num_iterations=2), _tiny(), "tiny detection, 64-D decoder")
 
 
 def test_cluster_fallback_on_a_lost_hand_off(eng):
@@ -478,6 +510,18 @@ def test_mixed_reuse_is_exact(eng):
     assert list(off[0][3]) == [0, 1, 0, 0]
     _assert_same_bits(off, on, np.array([0, 2, 3]), "mixed reuse, ragged batch")
     assert on[2]["n_render_rows"] > 0
+    # the smallest list (_tiny): a few forward + backward tiles and a few backward-only tiles, the last of each kind with a single or a few points
+    tiny = _tiny()
+    p2 = E.gn_params(num_iterations=2)
+    for prepass in (1, 0):
+        kw = dict(prepass=prepass, split_rows=1, speculative_band=0, cluster_tiles=0)
+        off = _run_traced(eng, p2, [tiny], 2, mixed_reuse=0, **kw)
+        on = _run_traced(eng, p2, [tiny], 2, mixed_reuse=1, **kw)
+        for r in (off, on):
+            _assert_not_degenerate(r, ("mixed reuse, tiny detection", prepass))
+        _assert_same_bits(off, on, np.array([0]), "mixed reuse, tiny detection, prepass %d" % prepass)
+        assert off[2]["n_render_rows"] == 0 and on[2]["n_render_rows"] > 0, (off[2]["n_render_rows"], on[2]["n_render_rows"])
+        assert on[2]["n_jac_points"] + on[2]["n_render_rows"] == off[2]["n_jac_points"]
     # mask reuse switched off as a whole turns the mixed form off too
     none = _run_traced(eng, prm, [big], n_it, mask_reuse=0)
     assert none[2]["n_render_rows"] == 0

@@ -611,13 +611,12 @@ def _flip_allowance(j, j_alt, rr, w):
     return a_h, a_b, int(rows.shape[0])
 
 
-def _robust64(res, b):
-    """get_robust_res in float64 -> (w * res, mean((w * res)^2))."""
+def _robust_rows64(res, b):
+    """get_robust_res's w * res in float64."""
     x = np.abs(res)
     rho = np.where(x <= b, x * x, 2.0 * b * x - b * b)
     w = np.sqrt(rho) / np.where(x == 0, 1.0, x)
-    rr = w * res
-    return rr, float(np.mean(rr * rr))
+    return w * res
 
 
 def _sim3_rows64(p):
@@ -633,42 +632,34 @@ def _sim3_rows64(p):
     return j
 
 
-def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
-    """One Gauss-Newton system of reconstruct_object (optimizer.py:129-186) evaluated in float64 throughout, at the state
-    (t_obj_cam, code) with the depth samples `depths`, on the sample sets the caller decided: sets = the fp32 trace's `sets`
-    (`valid` = in-sphere (ray, depth) indices, `kept` = rendered rows).  No threshold is re-applied here -- fp64 and fp32 may
-    decide a sample within round-off of a threshold differently, and the comparison is of arithmetic on one set.
-
-    Returns a dict: H, b, dx (the system and its solve), Dr / Ds (data Grams k1 J_r^T J_r / K and k2 J_s^T J_s / N, no prior, no
-    damping), gr / gs (data parts of b: -k1 J_r^T r_r / K, -k2 J_s^T r_s / N), Lr / Ls (k1 render_loss, k2 sdf_loss), the prior
-    terms H_code_prior (k3), b_code_prior (-k3 z), H_rot / b_rot (the k4 rotation prior as added to H and b), j_rot, H_damp (the
-    pose-block damping), V, K, N, loss.  H_flip / b_flip: what the surface and render rows with a hidden ReLU within round-off of its
-    kink (RELU_ULPS) would change in H and b, entry by entry, on the other side of it -- an fp32 implementation may land on either side,
-    and the gradient jumps there (n_flip = the number of such surface and render rows)."""
+def _view_rows64(dec, prm, pts, rays, depth, t_view, code, depths, sets):
+    """The float64 rows one view contributes to a Gauss-Newton system at its camera->object matrix t_view (loss.py:22-152): a dict of
+    j_s / j_r (surface and render jacobian rows, (n, 7 + code_len)), j_s2 / j_r2 (their twins on the other side of every ReLU kink within
+    round-off, _decoder_fb64), r_s / r_r (the robust residuals w * r of get_robust_res) and V, K, N.  sets as in linearise_fp64; a view
+    with an empty `kept` set, without rays or without points gives zero rows of that kind."""
     c_len = prm.code_len
     z = np.asarray(code, F64)[:c_len]
-    t = np.asarray(t_obj_cam, F32).astype(F64)
+    t = np.asarray(t_view, F32).astype(F64)
     r_m, t_v = t[:3, :3], t[:3, 3]
-    rays = np.asarray(rays, F32).astype(F64)
+    rays = np.asarray(rays, F32).astype(F64).reshape(-1, 3)
     d = np.asarray(depths, F32).astype(F64)[:prm.num_depth_samples]
     n_d = d.shape[0]
-    n_fg = np.asarray(depth).shape[0]
+    n_fg = np.asarray(depth).reshape(-1).shape[0]
     d_min, d_max = d[0], d[-1]
     c11 = float(F32(1.1))                                     # the reference's constants are float32 scalars
-    depth_obs = np.concatenate([np.asarray(depth, F32).astype(F64), np.full(rays.shape[0] - n_fg, c11 * d_max)])
+    depth_obs = np.concatenate([np.asarray(depth, F32).astype(F64).reshape(-1), np.full(rays.shape[0] - n_fg, c11 * d_max)])
     th = float(F32(prm.cut_off))
-    pd = 7
     # surface term (loss.py:22-43)
-    p_s = np.asarray(pts, F32).astype(F64) @ r_m.T + t_v
-    p_in = np.asarray(pts, F32).astype(F64)
+    p_in = np.asarray(pts, F32).astype(F64).reshape(-1, 3)
+    p_s = p_in @ r_m.T + t_v
     r_s, g_s, g_s2 = _decode64(dec, z, p_s, dp=EPS32 * (np.abs(p_in) @ np.abs(r_m).T + np.abs(t_v)))
     sim_s = _sim3_rows64(p_s)
     j_s = np.concatenate([np.einsum("ni,nij->nj", g_s[:, -3:], sim_s), g_s[:, :-3]], -1)
     j_s2 = np.concatenate([np.einsum("ni,nij->nj", g_s2[:, -3:], sim_s), g_s2[:, :-3]], -1)
-    rr_s, sdf_loss = _robust64(r_s, float(F32(prm.b2)))
+    rr_s = _robust_rows64(r_s, float(F32(prm.b2)))
     # render term (loss.py:46-152) on the given sets
-    vx, vy = (np.asarray(a) for a in sets["valid"])
-    gx, gy = (np.asarray(a) for a in sets["kept"])
+    vx, vy = (np.asarray(a, np.int64).reshape(-1) for a in sets["valid"])
+    gx, gy = (np.asarray(a, np.int64).reshape(-1) for a in sets["kept"])
     p_v = (rays[vx] * d[vy, None]) @ r_m.T + t_v
     sdf_v = _decode64(dec, z, p_v, grad=False)[0]
     occ = np.zeros((rays.shape[0], n_d), F64)
@@ -691,7 +682,21 @@ def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
     de_di, de_di2 = de_ds[:, None] * ds_di, de_ds[:, None] * ds_di2
     j_r = np.concatenate([np.einsum("ni,nij->nj", de_di[:, -3:], sim_k), de_di[:, :-3]], -1)
     j_r2 = np.concatenate([np.einsum("ni,nij->nj", de_di2[:, -3:], sim_k), de_di2[:, :-3]], -1)
-    rr_r, render_loss = _robust64(r_r, float(F32(prm.b1)))
+    rr_r = _robust_rows64(r_r, float(F32(prm.b1)))
+    return dict(j_s=j_s, j_s2=j_s2, r_s=rr_s, j_r=j_r, j_r2=j_r2, r_r=rr_r, V=int(vx.shape[0]), K=int(j_r.shape[0]), N=int(j_s.shape[0]))
+
+
+def _assemble64(prm, rows, t_obj_cam, code):
+    """The Gauss-Newton system of optimizer.py:153-186 in float64 from the rows of any number of views (_view_rows64), pooled as one row
+    set: data Grams and gradients over the pooled N and K, the losses and the kink allowances from the pooled rows, and the code prior,
+    rotation prior and damping once, at the object's own t_obj_cam.  A row kind nobody contributes to leaves its terms at zero."""
+    c_len = prm.code_len
+    z = np.asarray(code, F64)[:c_len]
+    t = np.asarray(t_obj_cam, F32).astype(F64)
+    pd = 7
+    n_unk = pd + c_len
+    one = len(rows) == 1
+    j_s, j_s2, rr_s, j_r, j_r2, rr_r = ((rows[0][k] if one else np.concatenate([r[k] for r in rows])) for k in ("j_s", "j_s2", "r_s", "j_r", "j_r2", "r_r"))
     # rotation prior (loss.py:155-178)
     t_co = np.linalg.inv(t)
     r_co = t_co[:3, :3] / np.cbrt(np.linalg.det(t_co[:3, :3]))
@@ -703,13 +708,20 @@ def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
         res_rot = 0.0
     k1, k2, k3, k4 = (float(F32(v)) for v in (prm.k1, prm.k2, prm.k3, prm.k4))
     n_s, n_k = j_s.shape[0], j_r.shape[0]
-    ds_ = k2 * _mm64(j_s.T, j_s) / n_s
-    dr_ = k1 * _mm64(j_r.T, j_r) / n_k
-    gs_ = -k2 * (j_s.T @ rr_s) / n_s
-    gr_ = -k1 * (j_r.T @ rr_r) / n_k
-    fh_s, fb_s, nf_s = _flip_allowance(j_s, j_s2, rr_s, k2 / n_s)
-    fh_r, fb_r, nf_r = _flip_allowance(j_r, j_r2, rr_r, k1 / n_k)
-    n_unk = pd + c_len
+    if n_s:
+        sdf_loss = float(np.mean(rr_s * rr_s))
+        ds_ = k2 * _mm64(j_s.T, j_s) / n_s
+        gs_ = -k2 * (j_s.T @ rr_s) / n_s
+        fh_s, fb_s, nf_s = _flip_allowance(j_s, j_s2, rr_s, k2 / n_s)
+    else:
+        sdf_loss, ds_, gs_, fh_s, fb_s, nf_s = 0.0, np.zeros((n_unk, n_unk)), np.zeros(n_unk), np.zeros((n_unk, n_unk)), np.zeros(n_unk), 0
+    if n_k:
+        render_loss = float(np.mean(rr_r * rr_r))
+        dr_ = k1 * _mm64(j_r.T, j_r) / n_k
+        gr_ = -k1 * (j_r.T @ rr_r) / n_k
+        fh_r, fb_r, nf_r = _flip_allowance(j_r, j_r2, rr_r, k1 / n_k)
+    else:
+        render_loss, dr_, gr_, fh_r, fb_r, nf_r = 0.0, np.zeros((n_unk, n_unk)), np.zeros(n_unk), np.zeros((n_unk, n_unk)), np.zeros(n_unk), 0
     h_code = np.zeros((n_unk, n_unk))
     h_code[pd:, pd:] = k3 * np.eye(c_len)
     b_code = np.zeros(n_unk)
@@ -726,7 +738,47 @@ def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
     return dict(H=h, b=b, dx=np.linalg.solve(h, b), Dr=dr_, Ds=ds_, gr=gr_, gs=gs_, Lr=k1 * render_loss, Ls=k2 * sdf_loss,
                 H_code_prior=h_code, b_code_prior=b_code, H_rot=h_rot, b_rot=b_rot, j_rot=j_rot, res_rot=res_rot, H_damp=h_damp,
                 H_flip=fh_s + fh_r, b_flip=fb_s + fb_r, n_flip=(nf_s, nf_r),
-                V=int(vx.shape[0]), K=int(n_k), N=int(n_s), loss=k1 * render_loss + k2 * sdf_loss)
+                V=int(sum(r["V"] for r in rows)), K=int(n_k), N=int(n_s), loss=k1 * render_loss + k2 * sdf_loss)
+
+
+def linearise_fp64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets):
+    """One Gauss-Newton system of reconstruct_object (optimizer.py:129-186) evaluated in float64 throughout, at the state
+    (t_obj_cam, code) with the depth samples `depths`, on the sample sets the caller decided: sets = the fp32 trace's `sets`
+    (`valid` = in-sphere (ray, depth) indices, `kept` = rendered rows).  No threshold is re-applied here -- fp64 and fp32 may
+    decide a sample within round-off of a threshold differently, and the comparison is of arithmetic on one set.
+
+    Returns a dict: H, b, dx (the system and its solve), Dr / Ds (data Grams k1 J_r^T J_r / K and k2 J_s^T J_s / N, no prior, no
+    damping), gr / gs (data parts of b: -k1 J_r^T r_r / K, -k2 J_s^T r_s / N), Lr / Ls (k1 render_loss, k2 sdf_loss), the prior
+    terms H_code_prior (k3), b_code_prior (-k3 z), H_rot / b_rot (the k4 rotation prior as added to H and b), j_rot, H_damp (the
+    pose-block damping), V, K, N, loss.  H_flip / b_flip: what the surface and render rows with a hidden ReLU within round-off of its
+    kink (RELU_ULPS) would change in H and b, entry by entry, on the other side of it -- an fp32 implementation may land on either side,
+    and the gradient jumps there (n_flip = the number of such surface and render rows).
+    The rows come from _view_rows64 and are put together by _assemble64, which linearise_fp64_multiview shares."""
+    return _assemble64(prm, [_view_rows64(dec, prm, pts, rays, depth, t_obj_cam, code, depths, sets)], t_obj_cam, code)
+
+
+NO_SETS = dict(valid=(np.zeros(0, np.int64), np.zeros(0, np.int64)), kept=(np.zeros(0, np.int64), np.zeros(0, np.int64)))
+
+
+def view_matrix(t_obj_cam, t_ref_cam):
+    """T_oc_v = T_oc T_ref_v: the fp64 product of the two fp32 matrices, rounded once to fp32."""
+    return (np.asarray(t_obj_cam, F32).astype(F64) @ np.asarray(t_ref_cam, F32).astype(F64)).astype(F32)
+
+
+def linearise_fp64_multiview(dec, prm, views, t_obj_cam, code, depths_per_view, sets_per_view, rows_out=None):
+    """linearise_fp64 for one object seen by several cameras: views = [dict(t_ref_cam, pts, rays, depth), ...]; view v's rows are
+    linearise_fp64's rows at view_matrix(t_obj_cam, t_ref_cam_v) on depths_per_view[v] and sets_per_view[v] (None, or empty `kept`: the
+    view has no render rows), and the rows of all views are pooled as one row set -- divided by the pooled N and K -- while the priors
+    and the damping are taken once at t_obj_cam.  Returns linearise_fp64's keys (V, K, N pooled) plus V_views / K_views / N_views.
+    rows_out (optional list) receives each view's rows (_view_rows64)."""
+    rows = []
+    for v, d, s in zip(views, depths_per_view, sets_per_view):
+        rows.append(_view_rows64(dec, prm, v["pts"], v["rays"], v["depth"], view_matrix(t_obj_cam, v["t_ref_cam"]), code, d, NO_SETS if s is None else s))
+    if rows_out is not None:
+        rows_out.extend(rows)
+    lin = _assemble64(prm, rows, t_obj_cam, code)
+    lin.update(V_views=[r["V"] for r in rows], K_views=[r["K"] for r in rows], N_views=[r["N"] for r in rows])
+    return lin
 
 
 def pose_only_system(dec, pts, t_obj_cam, code):

@@ -21,10 +21,12 @@ def view_state(t_obj_cam, t_ref_cam, n_depth):
     return t_v, O.linspace_f32(d_min, d_max, n_depth)
 
 
-def reconstruct_object_multiview(dec, prm, t_cam_obj, views, code=None, trace=None, t_obj_cam0=None, num_iterations=None, depths_override=None):
+def reconstruct_object_multiview(dec, prm, t_cam_obj, views, code=None, trace=None, t_obj_cam0=None, num_iterations=None, depths_override=None,
+                                 sdf_jitter=0.0):
     """views: [dict(t_ref_cam, pts, rays, depth), ...].  Returns dict(t_cam_obj, code, is_good, loss, status) -- status 0 good, 1 no view
     reached 10 in-sphere samples, 2 NaN / empty row set.  trace (list) receives one dict per iteration: pooled H, b, dx, loss, the state,
-    and per view V, K, vsum, ksum, depths, t_obj_cam."""
+    and per view V, K, vsum, ksum, depths, t_obj_cam, sets (compute_render_loss's stats: `valid`, `kept`, ...; None where the view's
+    render term is None).  sdf_jitter (tests only): passed to compute_render_loss -- the jitter twin of tests/test_gpu_parity.py."""
     c_len = prm.code_len
     z = np.zeros(c_len, F32) if code is None else np.asarray(code, F32)[:c_len].copy()
     t_obj_cam = O._inv(np.asarray(t_cam_obj, F32)) if t_obj_cam0 is None else np.asarray(t_obj_cam0, F32).copy()
@@ -42,8 +44,9 @@ def reconstruct_object_multiview(dec, prm, t_cam_obj, views, code=None, trace=No
                 j7, jc, r = O.compute_sdf_loss(dec, pts, t_v, z)                 # :129
                 rows_s.append((np.concatenate([j7, jc], -1), r))
             st = {"V": 0}
-            rend = O.compute_render_loss(dec, rays, depth_obs, t_v, sampled, z, th=prm.cut_off, stats=st) if rays.shape[0] else None
-            info = dict(V=st["V"], K=0, vsum=0, ksum=0, depths=sampled, t_obj_cam=t_v, none=rend is None)
+            rend = O.compute_render_loss(dec, rays, depth_obs, t_v, sampled, z, th=prm.cut_off, stats=st,
+                                         sdf_jitter=sdf_jitter) if rays.shape[0] else None
+            info = dict(V=st["V"], K=0, vsum=0, ksum=0, depths=sampled, t_obj_cam=t_v, none=rend is None, sets=None if rend is None else st)
             if rend is not None:
                 j7, jc, r = rend
                 rows_r.append((np.concatenate([j7, jc], -1), r))
@@ -124,6 +127,28 @@ def late_join_case(seed=61, n_depth=50):
     n0, ng = _insphere_per_ray(t0, rays, n_depth), _insphere_per_ray(tg, rays, n_depth)
     pick = np.where((n0 == 0) & (ng >= 2) & (ng <= 12))[0]
     rays = rays[pick][np.argsort(-ng[pick], kind="stable")][:24]
+    eye = np.eye(4, dtype=F32)
+    return o["t_cam_obj_init"], [dict(t_ref_cam=eye, pts=o["pts"], rays=o["rays"], depth=o["depth"]),
+                                 dict(t_ref_cam=eye, pts=np.zeros((0, 3), F32), rays=np.ascontiguousarray(rays), depth=np.zeros(0, F32))]
+
+
+LEAVING_SEED = 64          # chosen with the composed oracle (tests/test_multiview_metric.py asserts the transition it was chosen for)
+
+
+def leaving_case(seed=LEAVING_SEED, n_depth=50):
+    """late_join_case with the roles of the start and the generating pose swapped: the second view holds only background rays grazing the rim
+    of the unit sphere that are inside it at the (perturbed) start pose and outside it at the generating pose -- so that its render rows are
+    there in iteration 0 and vanish in a later one.  Geometry only; tests confirm the transition with the composed oracle."""
+    from dsp_slam_amd import synth
+    o = synth.make_object(seed, n_surface=150, n_background=40)
+    t0, tg = O._inv(o["t_cam_obj_init"]), O._inv(o["t_cam_obj_gt"])
+    c = o["t_cam_obj_gt"][:3, 3].astype(np.float64)
+    s = float(o["scale"])
+    u, v = np.meshgrid(np.linspace(-1.3, 1.3, 81), np.linspace(-1.3, 1.3, 81))
+    rays = np.stack([(c[0] + s * u.ravel()) / c[2], (c[1] + s * v.ravel()) / c[2], np.ones(u.size)], -1).astype(F32)
+    n0, ng = _insphere_per_ray(t0, rays, n_depth), _insphere_per_ray(tg, rays, n_depth)
+    pick = np.where((ng == 0) & (n0 >= 2) & (n0 <= 12))[0]
+    rays = rays[pick][np.argsort(-n0[pick], kind="stable")][:24]
     eye = np.eye(4, dtype=F32)
     return o["t_cam_obj_init"], [dict(t_ref_cam=eye, pts=o["pts"], rays=o["rays"], depth=o["depth"]),
                                  dict(t_ref_cam=eye, pts=np.zeros((0, 3), F32), rays=np.ascontiguousarray(rays), depth=np.zeros(0, F32))]

@@ -7,6 +7,12 @@ For every recorded state -- camera->object matrix, code and depth samples of ite
 golden_bench_cfg2x64.npz -- the fp32 oracle linearises on the recorded depth samples (this decides the sample sets, and its V and K must be
 the reference's), then oracle.dsp_oracle.linearise_fp64 evaluates the same system in float64 on those sets.
 
+    python tools/measure_gn_metric.py --multiview [golden] [cases] [faults]  # the multi-view tables of profiles/multiview_metric.md
+
+--multiview prints, against the pooled fp64 system (oracle.dsp_oracle.linearise_fp64_multiview) on the composed fp32 oracle's sets: the
+composed oracle, its sdf-jitter twin and the reference's recorded system at every iteration of golden_multiview_cars3.npz; every iteration
+of the composed oracle's own run on each case of tests/multiview_metric.py; and the six member-view faults with the max-norm verdict.
+
 --measure writes, per state, the scaled errors of the fp32 oracle's and of the reference's recorded system against fp64, without the
 sdf-jitter allowance (the numbers tests/gn_metric.py derives its TAU from).  CPU only; reads nothing outside the repository.
 """
@@ -73,12 +79,57 @@ def linearise(dec, prm, inputs, state):
     return it, O.linearise_fp64(dec, prm, *inputs, *state, it["sets"])
 
 
+def _worst(rec):
+    return "H %.1e b %.1e dx %.1e solve %.1e" % (max(rec["H"].values()), max(rec["b_pose"], rec["b_code"]), rec["dx"], rec["solve"])
+
+
+def multiview(parts):
+    import multiview_metric as X
+    import multiview_oracle as MV
+    decs = {"cars": decoder_for({"optimizer": {"code_len": 64}}), "chairs32": decoder_for({"optimizer": {"code_len": 32}})}
+    if "golden" in parts:
+        g = np.load(os.path.join(GOLD, "golden_multiview_cars3.npz"))
+        prm = O.GNParams.from_configs(json.loads(str(g["cfg_json"])))
+        views = MV.golden_views(g)
+        print("golden_multiview_cars3.npz: scaled errors against the pooled fp64 (no jitter allowance)")
+        for e in range(g["it_H"].shape[0]):
+            t0 = time.time()
+            it, itj, lin = X.linearise_at(decs["cars"], prm, views, g["it_t_obj_cam"][e], g["it_code"][e], g["it_depths"][e])
+            ref = dict(H=g["it_H"][e], b=g["it_b"][e], dx=g["it_dx"][e])
+            print("  it %d V %s K %s n_flip %s (%.1f s)" % (e, lin["V_views"], lin["K_views"], lin["n_flip"], time.time() - t0))
+            for who, s in (("oracle", it), ("jitter twin", itj), ("reference", ref)):
+                print("    %-12s %s" % (who, _worst(M.scaled_errors(s, lin, prm.k4))), flush=True)
+    if "cases" in parts:
+        for name, make in X.CASES.items():
+            case = make()
+            oprm = X.oracle_params(case)
+            for i, obj in enumerate(case["objects"]):
+                t0 = time.time()
+                run = X.own_run(decs[case["decoder"]], oprm, obj, case["n_it"])
+                print("%s object %d (%d views): %d iterations of the composed oracle's own run (%.1f s)" % (name, i, len(obj["views"]), len(run), time.time() - t0))
+                for e, (it, itj, lin) in enumerate(run):
+                    print("  it %d (V, K) %s M %d K %d jitter twin's sets %s n_flip %s: %s" % (
+                        e, X.view_vk(it), it["M"], it["K"], "same" if X.same_sets(it, itj) else "DIFFER", lin["n_flip"],
+                        _worst(M.scaled_errors(it, lin, oprm.k4))), flush=True)
+    if "faults" in parts:
+        for label, oprm, views, it, lin, prev_code in X.fault_states(decs["cars"]):
+            base = M.scaled_errors(it, lin, oprm.k4)
+            print("%s: unperturbed worst %.1e (%s)" % (label, base["worst"], "accepted" if M.within_tau(base) else "REJECTED"))
+            for what, sys_ in X.faults(decs["cars"], oprm, views, it, prev_code).items():
+                rec = M.scaled_errors(sys_, lin, oprm.k4)
+                print("  %-62s worst %.1e solve %.1e %-8s max-norm check: %s" % (
+                    what, rec["worst"], rec["solve"], "accepted" if M.within_tau(rec) else "rejected", "passes" if X.max_norm_passes(sys_, it, oprm.k4) else "fails"), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multiview", nargs="*", choices=["golden", "cases", "faults"], help="print the multi-view tables (default: all three)")
     ap.add_argument("--measure", help="write the per-state scaled errors of the oracle and the reference to this json")
     ap.add_argument("--recon-only", action="store_true", help="the golden_recon_* states only (not the 160 bench iterations)")
     ap.add_argument("--bench-only", action="store_true", help="the 160 bench iterations only")
     a = ap.parse_args()
+    if a.multiview is not None:
+        multiview(a.multiview or ["golden", "cases", "faults"])
     if a.measure:
         rows = []
         for case, e, dec, prm, inputs, state, ref, vk in (bench_states() if a.bench_only else recorded_states(a.recon_only)):

@@ -401,6 +401,23 @@ void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
                       const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr,
                       const PriorDev* prior = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
+// observation report (dsp_batch_report): the device arrays of one batch, in the order of the inputs -- points by pts_off, rays by ray_off,
+// 8 doubles per member.  launch_report runs k_report_rays / k_report_points / k_report_members behind the front of the pass at the
+// returned state; park (optional): k_report_members puts the parked status words back (the posterior is off: nobody else will).
+// report_ray_host: report_math::ray compiled for the host in the translation unit that has contraction off (dsp_debug_report_ray).
+struct ReportDev {
+    float* pt_sdf = nullptr;
+    unsigned char* pt_flags = nullptr;
+    float* ray_depth = nullptr;
+    float* ray_hit = nullptr;
+    float* ray_residual = nullptr;
+    int* ray_counts = nullptr;      // 3 per ray: in-sphere, band, kept
+    double* member = nullptr;       // 8 per member: M, V, m, K, sum_s, sum_r, status, 0
+};
+void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
+                   const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
+                   int maxM, int B, hipStream_t s);
+void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3);
 // the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass 1: e and chi2 at the returned
 // state instead; 2 (launch_solve with step control): the terms, and chi2 at the current state in the record's chi2 slot
 void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s);

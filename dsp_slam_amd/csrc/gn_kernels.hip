@@ -9,6 +9,7 @@
 // These kernels are HBM/latency-bound integer+float bookkeeping (< 0.5 % of the FLOPs); they exist so
 // that the whole iteration stays on the device with no host round trip.
 #include "dsp_internal.h"
+#include "report_math.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -626,6 +627,73 @@ __global__ __launch_bounds__(256) void k_tail_tiles(const int4* tiles, int* n_ti
 // time.  ~600 wave instructions per ray instead of ~7000 thread instructions, and every ray on its own SIMD.
 __device__ __forceinline__ float lane_value(float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); }
 
+// The three chains, one wave per ray (lane = depth index).  f = 1 - o_lane.  T_l = prod_{i<=l} (1 - o_i), sequential in l (torch.cumprod).
+__device__ __forceinline__ float wave_transmittance(float f, int lane, int n_depth) {
+    float Tj = 0.f, acc = 1.f;
+    for (int j = 0; j < n_depth; ++j) {
+        acc = __fmul_rn(acc, lane_value(f, j));
+        if (lane == j) Tj = acc;
+    }
+    return Tj;
+}
+// d_u = sum_l d_l * o_l * T_{l-1} + d_bg * T_{D-1}, summed front to back   (loss.py:100-114); term = this lane's d_l o_l T_{l-1}
+__device__ __forceinline__ float wave_rendered_depth(float term, float Tj, float d_bg, int n_depth) {
+    float du = 0.f;
+    for (int j = 0; j < n_depth; ++j) du = __fadd_rn(du, lane_value(term, j));
+    return __fadd_rn(du, __fmul_rn(d_bg, lane_value(Tj, n_depth - 1)));
+}
+// sum_{l>=k} T_l, the suffix sums accumulated back to front (the numerator of de_do_k, loss.py:118-121)
+__device__ __forceinline__ float wave_suffix_sums(float Tj, int lane, int n_depth) {
+    float Sj = 0.f, sacc = 0.f;
+    for (int j = n_depth - 1; j >= 0; --j) {
+        sacc = __fadd_rn(sacc, lane_value(Tj, j));
+        if (lane == j) Sj = sacc;
+    }
+    return Sj;
+}
+
+// One lane's view of its ray: the addressing (raymask / rayoff / ssdf), the occupancy, the three chains and the keep test -- everything
+// k_render_scan and k_report_rays (the observation report) have in common, so that the two cannot drift.  The per-sample steps are
+// report_math.h's, which the host's scalar statement of the ray (report_math::ray, dsp_debug_report_ray) calls as well.
+struct RayLane {
+    int base, k;            // the ray's compact sample run starts at base; this lane's sample is base + k (when in)
+    bool in, wg, keep;      // in the unit sphere / in the band -th < sdf < th (loss.py:88) / kept: de_do > 1e-2
+    float T_last;           // T_{D-1} (wave-uniform)
+    float du, res;          // rendered depth d_u and obs - d_u, unclipped (wave-uniform)
+    float dedo;             // de_do of a kept sample
+    unsigned long long mask;
+};
+__device__ __forceinline__ RayLane ray_lane(const ObjConst& c, const ObjState& s, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
+                                            const float* depth_fg, int gr, int r, int lane, int n_depth, float th) {
+    RayLane q;
+    q.mask = raymask[gr];
+    q.base = c.samp_off + rayoff[gr];
+    q.in = lane < n_depth && ((q.mask >> lane) & 1ull);
+    q.k = __popcll(q.mask & ((1ull << lane) - 1ull));
+    const float sd = q.in ? ssdf[q.base + q.k] : 0.f;
+    const float dj = s.depths[lane < n_depth ? lane : 0];
+    float oj = 0.f;
+    q.wg = false;
+    if (q.in) {
+        oj = report_math::occupancy(sd, th);
+        q.wg = report_math::in_band(sd, th);
+    }
+    const float f = report_math::pass_through(oj);  // 1 exactly where there is no sample
+    const float Tj = wave_transmittance(f, lane, n_depth);
+    const float d_bg = report_math::background_depth(s.depths[n_depth - 1]);
+    const float tprev = __shfl_up(Tj, 1);
+    const float term = report_math::depth_term(dj, oj, lane == 0 ? 1.f : tprev);
+    q.du = wave_rendered_depth(term, Tj, d_bg, n_depth);
+    q.T_last = lane_value(Tj, n_depth - 1);
+    const float obs = (r < c.n_fg) ? depth_fg[c.depth_off + r] : d_bg;   // optimizer.py:126
+    q.res = __fsub_rn(obs, q.du);
+    // de_do_k = sum_{l>=k} T_l / (1 - o_k); keep > 1e-2  (loss.py:118-124)
+    const float Sj = wave_suffix_sums(Tj, lane, n_depth);
+    q.dedo = 0.f;
+    q.keep = q.wg && report_math::keep_sample(Sj, oj, q.dedo);
+    return q;
+}
+
 __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff,
                               const float* ssdf, const float* depth_fg, float* sdeds, float* ray_res, int* kcnt, int* mcnt,
                               int n_depth, float th) {
@@ -645,56 +713,17 @@ __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjStat
         if (lane == 0) { kcnt[gr] = 0; mcnt[gr] = 0; }
         return;
     }
-    const unsigned long long mask = raymask[gr];
-    const int base = c.samp_off + rayoff[gr];
-    const bool in = lane < n_depth && ((mask >> lane) & 1ull);
-    const int k = __popcll(mask & ((1ull << lane) - 1ull));
-    const float sd = in ? ssdf[base + k] : 0.f;
-    const float dj = s.depths[lane < n_depth ? lane : 0];
-    float oj = 0.f;
-    bool wg = false;                     // with_grad: -th < sdf < th  (loss.py:88)
-    if (in) {
-        const float cl = fminf(fmaxf(sd, -th), th);
-        oj = __fsub_rn(0.5f, __fdiv_rn(cl, __fmul_rn(2.f, th)));   // sdf_to_occupancy (loss_utils.py:40-48)
-        wg = sd > -th && sd < th;
-    }
-    const float f = __fsub_rn(1.f, oj);  // 1 exactly where there is no sample
-    // T_l = prod_{i<=l} (1 - o_i), sequential in l (torch.cumprod)
-    float Tj = 0.f, acc = 1.f;
-    for (int j = 0; j < n_depth; ++j) {
-        acc = __fmul_rn(acc, lane_value(f, j));
-        if (lane == j) Tj = acc;
-    }
-    const float d_bg = __fmul_rn(1.1f, s.depths[n_depth - 1]);
-    // d_u = sum_l d_l * o_l * T_{l-1} + d_bg * T_{D-1}, summed front to back   (loss.py:100-114)
-    const float tprev = __shfl_up(Tj, 1);
-    const float term = __fmul_rn(dj, __fmul_rn(oj, lane == 0 ? 1.f : tprev));
-    float du = 0.f;
-    for (int j = 0; j < n_depth; ++j) du = __fadd_rn(du, lane_value(term, j));
-    du = __fadd_rn(du, __fmul_rn(d_bg, lane_value(Tj, n_depth - 1)));
-    const float obs = (r < c.n_fg) ? depth_fg[c.depth_off + r] : d_bg;   // optimizer.py:126
-    float res = __fsub_rn(obs, du);
+    const RayLane q = ray_lane(c, s, raymask, rayoff, ssdf, depth_fg, gr, r, lane, n_depth, th);
     // loss.py:139-140 as written there -- `res_d[res_d > 0.30] = 0.30; res_d[res_d < -0.30] = -0.30` -- NOT fminf / fmaxf: a NaN residual (a NaN
     // observed depth) compares false twice and stays NaN, the render loss turns NaN and the object fails (optimizer.py:149-150); fminf / fmaxf
     // would turn it into a valid 0.30 (found by tests/test_gpu_errors.py).  Identical bits for every finite or infinite residual.
-    res = res > 0.30f ? 0.30f : res;
-    res = res < -0.30f ? -0.30f : res;
-    // de_do_k = sum_{l>=k} T_l / (1 - o_k), the suffix sums accumulated back to front; keep > 1e-2;
+    const float res = report_math::clip_residual(q.res);
     // de_ds = de_do * delta_d * (-1/(2 th))  (loss.py:118-130)
-    float Sj = 0.f, sacc = 0.f;
-    for (int j = n_depth - 1; j >= 0; --j) {
-        sacc = __fadd_rn(sacc, lane_value(Tj, j));
-        if (lane == j) Sj = sacc;
-    }
-    const float delta_d = __fdiv_rn(__fsub_rn(s.depths[n_depth - 1], s.depths[0]), (float)(n_depth - 1));
-    const float do_ds = __fdiv_rn(-1.f, __fmul_rn(2.f, th));
-    float deds = 0.f;
-    bool keep = false;
-    if (wg) {
-        const float dedo = __fdiv_rn(Sj, __fsub_rn(1.f, oj));
-        if (dedo > 1e-2f) { deds = __fmul_rn(__fmul_rn(dedo, delta_d), do_ds); keep = true; }
-    }
-    if (in) sdeds[base + k] = deds;      // never exactly 0 for a kept sample (dedo > 0.01, delta_d > 0)
+    const float delta_d = report_math::depth_step(s.depths[0], s.depths[n_depth - 1], n_depth);
+    const float do_ds = report_math::occupancy_slope(th);
+    const float deds = q.keep ? report_math::de_ds(q.dedo, delta_d, do_ds) : 0.f;
+    const bool in = q.in, wg = q.wg, keep = q.keep;
+    if (in) sdeds[q.base + q.k] = deds;      // never exactly 0 for a kept sample (dedo > 0.01, delta_d > 0)
     const unsigned long long keptm = __ballot(keep), wgm = __ballot(wg);
     unsigned khash = keep ? id_hash(((unsigned)r << 6) | (unsigned)lane) : 0u;
 #pragma unroll
@@ -704,6 +733,114 @@ __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjStat
         kcnt[gr] = __popcll(keptm);
         mcnt[gr] = __popcll(wgm);
         if (khash) atomicAdd(&st[b].ksum, khash);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// observation report (dsp_batch_report): what the pass at the RETURNED state leaves per ray, per surface point and per member
+// ------------------------------------------------------------------------------------------------
+// The three kernels run behind the front (and the Gram launch) of the pass that the posterior shares, on the arrays that front left, and
+// write report arrays only: nothing an iteration, k_posterior or k_finalize reads.  A member that is not part of a partial re-run
+// (DSP_STATUS_SKIP) keeps the rows of the run that produced its result row.
+//
+// k_report_rays: one wave per ray, lane = depth index -- k_render_scan's ray (ray_lane above), for EVERY ray, with the residual unclipped.
+// A member that is not good at the pass, or has < 10 in-sphere samples there (no render term: loss.py:73-74), gets NaN and zero counts.
+__global__ __launch_bounds__(256) void k_report_rays(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff,
+                                                     const float* ssdf, const float* depth_fg, int n_depth, float th, float* ray_depth, float* ray_hit,
+                                                     float* ray_residual, int* ray_counts) {
+    const int b = blockIdx.y;
+    const ObjConst c = oc[b];
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);     // wave-uniform
+    if (r >= c.n_rays) return;
+    const ObjState& s = st[b];
+    if (s.status == DSP_STATUS_SKIP) return;
+    const int gr = c.ray_off + r;
+    if (s.status != DSP_STATUS_GOOD || s.V < 10) {
+        if (lane == 0) {
+            ray_depth[gr] = ray_hit[gr] = ray_residual[gr] = __int_as_float(0x7fc00000);
+            ray_counts[3 * gr] = ray_counts[3 * gr + 1] = ray_counts[3 * gr + 2] = 0;
+        }
+        return;
+    }
+    const RayLane q = ray_lane(c, s, raymask, rayoff, ssdf, depth_fg, gr, r, lane, n_depth, th);
+    const unsigned long long keptm = __ballot(q.keep), wgm = __ballot(q.wg);
+    if (lane == 0) {
+        ray_depth[gr] = q.du;
+        ray_hit[gr] = __fsub_rn(1.f, q.T_last);
+        ray_residual[gr] = q.res;
+        ray_counts[3 * gr] = __popcll(n_depth < 64 ? q.mask & ((1ull << n_depth) - 1ull) : q.mask);
+        ray_counts[3 * gr + 1] = __popcll(wgm);
+        ray_counts[3 * gr + 2] = __popcll(keptm);
+    }
+}
+
+// k_report_points: the decoder value the pass's jacobian launch left for every surface point (the residual of compute_sdf_loss,
+// loss.py:22-43), and bit 0 of the flags = the point is alive (pose-only batches: the inlier filter's mask; always set elsewhere).
+// A view with < 10 in-sphere samples still contributes its surface points (k_render_scan), so its points are reported.
+__global__ __launch_bounds__(256) void k_report_points(const ObjConst* oc, const ObjState* st, const float* jgrad, const unsigned char* alive, float* pt_sdf,
+                                                       unsigned char* pt_flags) {
+    const int b = blockIdx.y;
+    const ObjConst c = oc[b];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c.n_pts) return;
+    const int status = st[b].status;
+    if (status == DSP_STATUS_SKIP) return;
+    if (status != DSP_STATUS_GOOD) { pt_sdf[c.pts_off + i] = __int_as_float(0x7fc00000); pt_flags[c.pts_off + i] = 0; return; }
+    const int idx = c.jsdf_off + i;
+    pt_sdf[c.pts_off + i] = jgrad[(size_t)idx * GRAD_STRIDE + 67];
+    pt_flags[c.pts_off + i] = (alive == nullptr || alive[idx]) ? 1 : 0;
+}
+
+// k_report_members: one workgroup per member.  out (8 doubles) = M, V, m, K, sum_s, sum_r, status, 0: the counts of the pass, and the sums
+// of (w r)^2 over the member's surface rows (Huber b_sdf) and over its kept render rows (Huber b_render) -- each w r the float32 last
+// column of the jacobian row as k_gram builds it (robust = 0, pose-only batches: r itself, over the alive points), squared and summed in
+// fp64: every thread a strided partial sum, then a fixed tree.  park (optional): the member's parked status word goes back afterwards --
+// what k_posterior does when the posterior is on.
+__global__ __launch_bounds__(256) void k_report_members(const ObjConst* oc, ObjState* st, const float2* jaux, const float* jgrad, const unsigned char* alive,
+                                                        float b_sdf, float b_render, int robust, int pose_only, const int* park, double* out) {
+    __shared__ double part[2][256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const ObjConst c = oc[b];
+    ObjState& s = st[b];
+    const int status = s.status;
+    if (status == DSP_STATUS_SKIP) return;          // (a parked SKIP is a SKIP: k_posterior_park leaves it)
+    const bool good = status == DSP_STATUS_GOOD;
+    const bool render = good && !pose_only && s.V >= 10;
+    const int K = render ? s.K : 0;
+    double acc_s = 0.0, acc_r = 0.0;
+    if (good) {
+        for (int i = tid; i < c.n_pts; i += 256) {
+            const int idx = c.jsdf_off + i;
+            if (alive && !alive[idx]) continue;
+            const float r = jgrad[(size_t)idx * GRAD_STRIDE + 67];
+            const double wr = (double)(robust ? report_math::robust_residual(r, b_sdf) : r);
+            acc_s = __dadd_rn(acc_s, __dmul_rn(wr, wr));
+        }
+        for (int i = tid; i < K; i += 256) {
+            const float r = jaux[c.jren_off + i].y;
+            const double wr = (double)(robust ? report_math::robust_residual(r, b_render) : r);
+            acc_r = __dadd_rn(acc_r, __dmul_rn(wr, wr));
+        }
+    }
+    part[0][tid] = acc_s; part[1][tid] = acc_r;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (tid < d) { part[0][tid] = __dadd_rn(part[0][tid], part[0][tid + d]); part[1][tid] = __dadd_rn(part[1][tid], part[1][tid + d]); }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double* o = out + (size_t)b * 8;
+        const int M = !good ? 0 : (pose_only ? (s.n_alive >= 0 ? s.n_alive : c.n_pts) : c.n_pts);
+        o[0] = (double)M;
+        o[1] = good && !pose_only ? (double)s.V : 0.0;
+        o[2] = render ? (double)s.m : 0.0;
+        o[3] = (double)K;
+        o[4] = good ? part[0][0] : nan("");
+        o[5] = good ? part[1][0] : nan("");
+        o[6] = (double)(good ? ((!pose_only && s.V < 10) ? DSP_STATUS_FEW : DSP_STATUS_GOOD) : status);
+        o[7] = 0.0;
+        if (park) s.status = park[b];
     }
 }
 
@@ -959,14 +1096,8 @@ __device__ __forceinline__ void build_row(const float* g68, float4 p, float2 aux
     row[5] = __fadd_rn(__fmul_rn(-p.y, d0), __fmul_rn(p.x, d1));
     row[6] = __fadd_rn(__fadd_rn(__fmul_rn(p.x, d0), __fmul_rn(p.y, d1)), __fmul_rn(p.z, d2));
     for (int i = 0; i < 64; ++i) row[7 + i] = __fmul_rn(sc, g68[i]);
-    float rr = r;
-    if (robust) {   // huber_norm_weights: w = sqrt(rho)/|r|, only the residual is reweighted (loss_utils.py:236-265)
-        const float a = fabsf(r);
-        const float rho = (a <= huber_b) ? __fmul_rn(a, a) : __fsub_rn(__fmul_rn(__fmul_rn(2.f, huber_b), a), __fmul_rn(huber_b, huber_b));
-        const float w = (a == 0.f) ? 0.f : __fdiv_rn(__fsqrt_rn(rho), a);
-        rr = __fmul_rn(w, r);
-    }
-    row[71] = rr;
+    // huber_norm_weights: w = sqrt(rho)/|r|, only the residual is reweighted (loss_utils.py:236-265)
+    row[71] = robust ? report_math::robust_residual(r, huber_b) : r;
 }
 
 constexpr int GRAM_PTS = 32;    // granularity of a slice's share of the rows (part of the summation grouping: do not change)
@@ -1043,14 +1174,8 @@ __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState
                         row[4] = __fadd_rn(__fmul_rn(p.z, d0), __fmul_rn(-p.x, d2));
                         row[5] = __fadd_rn(__fmul_rn(-p.y, d0), __fmul_rn(p.x, d1));
                         row[6] = __fadd_rn(__fadd_rn(__fmul_rn(p.x, d0), __fmul_rn(p.y, d1)), __fmul_rn(p.z, d2));
-                        float rr = res;
-                        if (robust) {   // huber_norm_weights: w = sqrt(rho)/|r|, only the residual is reweighted (loss_utils.py:236-265)
-                            const float a = fabsf(res);
-                            const float rho = (a <= hb) ? __fmul_rn(a, a) : __fsub_rn(__fmul_rn(__fmul_rn(2.f, hb), a), __fmul_rn(hb, hb));
-                            const float w = (a == 0.f) ? 0.f : __fdiv_rn(__fsqrt_rn(rho), a);
-                            rr = __fmul_rn(w, res);
-                        }
-                        row[71] = rr;
+                        // huber_norm_weights: w = sqrt(rho)/|r|, only the residual is reweighted (loss_utils.py:236-265)
+                        row[71] = robust ? report_math::robust_residual(res, hb) : res;
                     }
                 } else {
 #pragma unroll
@@ -2232,6 +2357,20 @@ void launch_render_scan(const ObjConst* oc, ObjState* st, const unsigned long lo
                         float* sdeds, float* ray_res, int* kcnt, int* mcnt, int D, float th, int maxR, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_render_scan, dim3((unsigned)std::max(1, (maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, st, m, off, ssdf, depth, sdeds, ray_res,
                        kcnt, mcnt, D, th);     // one wave per ray
+}
+void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
+                   const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
+                   int maxM, int B, hipStream_t s) {
+    if (!prm.pose_only && maxR > 0)
+        hipLaunchKernelGGL(k_report_rays, dim3((unsigned)((maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, (const ObjState*)st, raymask, rayoff, ssdf, depth_fg,
+                           prm.n_depth, prm.cut_off, rp.ray_depth, rp.ray_hit, rp.ray_residual, rp.ray_counts);     // one wave per ray
+    if (maxM > 0)
+        hipLaunchKernelGGL(k_report_points, GRID2(maxM, B), dim3(256), 0, s, oc, (const ObjState*)st, jgrad, alive, rp.pt_sdf, rp.pt_flags);
+    hipLaunchKernelGGL(k_report_members, dim3(B), dim3(256), 0, s, oc, st, jaux, jgrad, alive, prm.b2, prm.b1, prm.pose_only ? 0 : 1, prm.pose_only, park,
+                       rp.member);
+}
+void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3) {
+    report_math::ray(n_depth, depths, sdf, th, depth_obs, is_fg, out4, counts3);
 }
 void launch_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff, const float4* spts,
                          const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s) {

@@ -175,6 +175,48 @@ class Batch(object):
         out["var_code"] = np.ascontiguousarray(out["var_code"][:, :self.engine.code_len])
         return out
 
+    # ---- observation report (dsp_batch_report, include/dsp_gn.h): every observation once more at the returned state; changes no result ------
+    def set_report(self, on=True):
+        """on: the following runs evaluate every surface point and every ray once more at the state they return and keep the values on the
+        device for report().  False = off, the initial state."""
+        L.check(L.load().dsp_batch_report(self._h, int(bool(on))), self.engine._h, "dsp_batch_report")
+
+    def report(self):
+        """The last run's observation report (dsp_batch_report_fetch), concatenated in MEMBER order -- a member is an object, or a view of a
+        multi-view batch: dict(pt_sdf float32 (n_points,), pt_alive bool (n_points,) -- bit 0 of the flags, pt_flags uint8, ray_depth /
+        ray_hit / ray_residual float32 (n_rays,), ray_counts int32 (n_rays, 3) = in-sphere, band, kept samples, and per member M, V, m, K
+        int64, sum_s / sum_r float64, status int32; pts_off / ray_off / depth_off int64 (n_members + 1) cut the rows per member
+        (depth_off: its foreground rays come first, depth_off[i + 1] - depth_off[i] of them) and view_off int64 (n_objects + 1) the
+        members per object."""
+        lib, h = L.load(), self.engine._h
+        n_p, n_r, n_m = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(lib.dsp_batch_report_sizes(self._h, C.byref(n_p), C.byref(n_r), C.byref(n_m)), h, "dsp_batch_report_sizes")
+        n_p, n_r, n_m = n_p.value, n_r.value, n_m.value
+        out = dict(pt_sdf=np.zeros(n_p, np.float32), pt_flags=np.zeros(n_p, np.uint8), ray_depth=np.zeros(n_r, np.float32),
+                   ray_hit=np.zeros(n_r, np.float32), ray_residual=np.zeros(n_r, np.float32), ray_counts=np.zeros((n_r, 3), np.int32))
+        member = np.zeros((n_m, 8))
+        L.check(lib.dsp_batch_report_fetch(self._h, L.ptr(out["pt_sdf"]), L.ptr(out["pt_flags"], C.POINTER(C.c_uint8)), L.ptr(out["ray_depth"]),
+                                           L.ptr(out["ray_hit"]), L.ptr(out["ray_residual"]), L.ptr(out["ray_counts"], L.c_i32p),
+                                           L.ptr(member, L.c_f64p)), h, "dsp_batch_report_fetch")
+        out["pt_alive"] = (out["pt_flags"] & 1).astype(bool)
+        for i, k in enumerate(("M", "V", "m", "K")):
+            out[k] = member[:, i].astype(np.int64)
+        out["sum_s"], out["sum_r"] = member[:, 4].copy(), member[:, 5].copy()
+        out["status"] = member[:, 6].astype(np.int32)
+        out.update(self._member_offsets(n_m))
+        return out
+
+    def _member_offsets(self, n_members):
+        """pts_off / ray_off / depth_off per member as they were uploaded, and view_off (every object one member)."""
+        if self.pose_only:
+            zeros = np.zeros(n_members + 1, np.int64)
+            offs = dict(pts_off=np.asarray(self._keep[0], np.int64).copy(), ray_off=zeros, depth_off=zeros.copy())
+        else:
+            (po, _), (ro, _), (do, _) = self._keep[0], self._keep[1], self._keep[2]
+            offs = dict(pts_off=po.copy(), ray_off=ro.copy(), depth_off=do.copy())
+        offs["view_off"] = np.arange(n_members + 1, dtype=np.int64)
+        return offs
+
     # ---- Gaussian prior on pose and code (dsp_batch_prior, include/dsp_gn.h): fuse an earlier estimate into the run -------------------------
     def set_prior(self, t_obj_cam0=None, code0=None, Lambda=None):
         """Per object: t_obj_cam0 (4, 4) camera -> object, code0 (code_len or 64; ignored by pose-only batches), Lambda (71, 71) float64
@@ -373,8 +415,8 @@ def _step_control_args(step_control):
     return dict(zip(("lambda0", "up", "down", "lambda_min", "lambda_max"), step_control))
 
 
-def _run_resident(b, convergence, posterior, prior, step_control=None):
-    """The optional rules of the Engine's one-call forms on a resident batch: -> results() [+ (posterior(),)] [+ (prior_residual(),)]."""
+def _run_resident(b, convergence, posterior, prior, step_control=None, report=None):
+    """The optional rules of the Engine's one-call forms on a resident batch: -> results() [+ (posterior(),)] [+ (report(),)] [+ (prior_residual(),)]."""
     if convergence is not None:
         b.set_convergence(*convergence)
     if step_control is not None and step_control is not False:
@@ -383,8 +425,11 @@ def _run_resident(b, convergence, posterior, prior, step_control=None):
         b.set_posterior(*_posterior_args(posterior))
     if prior is not None:
         b.set_prior(*_prior_args(prior))
+    if report:
+        b.set_report(True)
     b.run()
-    return b.results() + (() if posterior is None else (b.posterior(),)) + (() if prior is None else (b.prior_residual(),))
+    return (b.results() + (() if posterior is None else (b.posterior(),)) + ((b.report(),) if report else ()) +
+            (() if prior is None else (b.prior_residual(),)))
 
 
 def _prior_lambda(lam, n):
@@ -442,6 +487,11 @@ class MultiviewBatch(Batch):
         engine._batches.add(self)
         if trace:
             L.check(lib.dsp_batch_enable_trace(self._h, 1), engine._h, "dsp_batch_enable_trace")
+
+    def _member_offsets(self, n_members):
+        """The members are the views: offsets per view, view_off per object (Batch.report)."""
+        vo, _, (po, _), (ro, _), (do, _) = self._keep[:5]
+        return dict(pts_off=po.copy(), ray_off=ro.copy(), depth_off=do.copy(), view_off=np.asarray(vo, np.int64).copy())
 
     def set_start_state(self, t_obj_cam=None, codes=None, depths=None):
         """t_obj_cam / codes: one per object; depths: one row per VIEW (all objects' views in order)."""
@@ -753,7 +803,7 @@ class Engine(object):
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
     def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, step_control=None, posterior=None,
-                          prior=None):
+                          report=None, prior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
         convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
         posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
@@ -761,15 +811,17 @@ class Engine(object):
         prior: None, or dict(t_obj_cam, code, Lambda) / (t_obj_cam0, code0, Lambda) of per-object arrays -- Batch.set_prior; the call then
         returns Batch.prior_residual() as its LAST item (behind the posterior, where both are asked for).
         step_control: None (off), True (the defaults), a dict of Batch.set_step_control's keyword arguments or a (lambda0, up, down,
-        lambda_min, lambda_max) tuple; the returned items are the same, `loss` is then the loss AT the returned state."""
+        lambda_min, lambda_max) tuple; the returned items are the same, `loss` is then the loss AT the returned state.
+        report: None / False, or True -- Batch.set_report; the call then returns Batch.report() behind the posterior (in front of the prior's
+        residual, which stays last)."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
-            return empty + (() if posterior is None else ({},)) + (() if prior is None else ({},))
+            return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
         b = Batch(self, prm, t_cam_obj, pts, rays, depth, codes)
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
-            return _run_resident(b, convergence, posterior, prior, step_control)
+            return _run_resident(b, convergence, posterior, prior, step_control, report)
         finally:
             b.close()
 
@@ -777,18 +829,18 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, prior=None):
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, report=None, prior=None):
         """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
         convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call.
-        posterior, prior: as reconstruct_batch (a resident batch too; further items, per object)."""
+        posterior, report, prior: as reconstruct_batch (a resident batch too; further items, per object -- the report's rows per VIEW)."""
         n = len(views)
         if n == 0:
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
-            return empty + (() if posterior is None else ({},)) + (() if prior is None else ({},))
-        if convergence is not None or posterior is not None or prior is not None:
+            return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
+        if convergence is not None or posterior is not None or prior is not None or report:
             b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
             try:
-                return _run_resident(b, convergence, posterior, prior)
+                return _run_resident(b, convergence, posterior, prior, None, report)
             finally:
                 b.close()
         vo, t_ref, pts, rays, depth = _flatten_views(views)
@@ -804,18 +856,19 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, prior=None):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, report=None, prior=None):
         """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
         one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior()).
+        report: as reconstruct_batch; Batch.report() follows the posterior (the alive bits are the inlier filter's mask).
         prior: as reconstruct_batch, with (6, 6) Lambdas and t_obj_cam0 carrying the scale; Batch.prior_residual() is then the last item."""
         n = len(pts)
         if n == 0:
-            extra = (() if posterior is None else ({},)) + (() if prior is None else ({},))
+            extra = (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
             return np.zeros((0, 4, 4), np.float32) if not extra else (np.zeros((0, 4, 4), np.float32),) + extra
-        if convergence is not None or posterior is not None or prior is not None:
+        if convergence is not None or posterior is not None or prior is not None or report:
             b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
             try:
-                res = _run_resident(b, convergence, posterior, prior)
+                res = _run_resident(b, convergence, posterior, prior, None, report)
                 return res[0] if len(res) == 4 else (res[0],) + res[4:]
             finally:
                 b.close()

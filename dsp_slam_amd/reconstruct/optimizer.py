@@ -13,6 +13,7 @@ from reconstruct.utils import ForceKeyErrorDict, create_voxel_grid, convert_sdf_
 from reconstruct.loss_utils import get_time
 from dsp_slam_amd import engine as _engine
 from dsp_slam_amd import _lib as _L
+from dsp_slam_amd import observations as _observations
 
 
 def _f32(a):
@@ -104,6 +105,21 @@ class Optimizer(object):
                 if len(sc) != 5:
                     raise ValueError("optimizer.joint_optim.step_control as a list is [lambda0, up, down, lambda_min, lambda_max]")
         self.step_control_joint = None if sc is None or sc is False else sc
+        # ADDITION (not in the reference's configs): "report": true under "joint_optim" / "pose_only_optim" switches the observation report on
+        # (dsp_batch_report): every surface point and ray evaluated once more at the returned state; good results then carry `observations`,
+        # the object's rows (dsp_slam_amd.observations reads them).  Read with a membership test like the keys above; absent or false means off.
+        def optional_flag(block):
+            try:
+                return bool(block["report"]) if "report" in block else False
+            except TypeError:
+                return False
+        self.report_joint = optional_flag(joint)
+        self.report_pose_only = False
+        try:
+            if "pose_only_optim" in optim_cfg:
+                self.report_pose_only = optional_flag(optim_cfg["pose_only_optim"])
+        except TypeError:
+            pass
 
     def _params(self):
         return _engine.gn_params(self.k1, self.k2, self.k3, self.k4, self.b1, self.b2, self.lr, self.s_damp,
@@ -131,10 +147,13 @@ class Optimizer(object):
         """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses.  return_posterior=True: (poses,
         Batch.posterior() dict) -- 6 x 6 pose information / covariance per object, with the weights of pose_only_optim.posterior ("mean" if absent).
         priors: None, or one dict(t_obj_cam (4, 4) with the scale in it, Lambda (6, 6)) or None per object (dsp_batch_prior); the call then
-        returns Batch.prior_residual() as its last item."""
+        returns Batch.prior_residual() as its last item.  With pose_only_optim.report set the call returns Batch.report() (per-point sdf and
+        the inlier filter's alive bits) behind the posterior, in front of the prior's residual."""
         kw = {} if self.convergence_pose_only is None else {"convergence": self.convergence_pose_only}
         if return_posterior:
             kw["posterior"] = self.posterior_pose_only or "mean"
+        if self.report_pose_only:
+            kw["report"] = True
         if priors is not None:
             kw["prior"] = self._stack_priors(priors, 6, self.code_len)
         return self.decoder.engine.estimate_pose_batch(self._params(), [_f32(t) for t in t_co_se3_list], scales,
@@ -146,11 +165,16 @@ class Optimizer(object):
         code: the object's shape code.  Returns the refined rigid object-to-camera matrix as a (4, 4) CPU torch.Tensor, like the reference.
         prior (an addition): dict(t_obj_cam, Lambda (6, 6)) -- the last estimate of this object and its information (one row of a pose-only
         Batch.posterior() at level 2); the call then returns a dict: t_cam_obj (the tensor), prior_chi2, prior_residual (6,)."""
-        if prior is None:
+        if prior is None and not self.report_pose_only:
             out = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code])
             return torch.from_numpy(out[0].copy())
-        out, res = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], priors=[prior])
-        return ForceKeyErrorDict(t_cam_obj=torch.from_numpy(out[0].copy()), prior_chi2=float(res["chi2"][0]), prior_residual=res["e"][0].copy())
+        ret = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], priors=None if prior is None else [prior])
+        extra = {}
+        if self.report_pose_only:       # (an addition, like the prior: the call then returns a dict)
+            extra["observations"] = _observations.object_rows(ret[1], 0)
+        if prior is not None:
+            extra.update(prior_chi2=float(ret[-1]["chi2"][0]), prior_residual=ret[-1]["e"][0].copy())
+        return ForceKeyErrorDict(t_cam_obj=torch.from_numpy(ret[0][0].copy()), **extra)
 
     # ---- joint shape + pose (reference optimizer.py:88-203) -----------------------------------------
     def reconstruct_objects(self, t_cam_obj_list, pts_list, rays_list, depth_list, codes=None, priors=None):
@@ -167,6 +191,8 @@ class Optimizer(object):
             kw["prior"] = self._stack_priors(priors, 71, self.code_len)
         if self.step_control_joint is not None:
             kw["step_control"] = self.step_control_joint
+        if self.report_joint:
+            kw["report"] = True
         res = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
             [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)
@@ -175,7 +201,8 @@ class Optimizer(object):
         for i in range(B):
             if status[i] == _L.OBJ_GOOD:
                 out.append(ForceKeyErrorDict(t_cam_obj=t[i].copy(), code=code[i].copy(), is_good=True,
-                                             loss=torch.tensor(float(loss[i])), **self._posterior_fields(res, i), **self._prior_fields(res, i, priors)))
+                                             loss=torch.tensor(float(loss[i])), **self._posterior_fields(res, i), **self._report_fields(res, i),
+                                             **self._prior_fields(res, i, priors)))
             else:   # reference: t_cam_obj=None, code=None, is_good=False, loss=<last computed loss> (:131,136,143,150)
                 out.append(ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[i])))
         return out
@@ -188,6 +215,12 @@ class Optimizer(object):
         return dict(pose_information=post["info_pose"][i].copy(), pose_covariance=post["cov_pose"][i].copy(),
                     code_variance=post["var_code"][i].copy(), loss_at_result=float(post["loss"][i]),
                     posterior_ok=bool(post["status"][i] == _L.POSTERIOR_OK))
+
+    def _report_fields(self, res, i):
+        """`observations` of a good object when joint_optim.report is set (nothing otherwise): Batch.report() follows the posterior."""
+        if not self.report_joint:
+            return {}
+        return dict(observations=_observations.object_rows(res[4 if self.posterior_joint is None else 5], i))
 
     @staticmethod
     def _prior_fields(res, i, priors):
@@ -224,11 +257,13 @@ class Optimizer(object):
         priors = None if prior is None else [prior]
         if priors is not None:
             kw["prior"] = self._stack_priors(priors, 71, self.code_len)
+        if self.report_joint:
+            kw["report"] = True
         res = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
         t, z, loss, status = res[:4]
         if status[0] == _L.OBJ_GOOD:
             return ForceKeyErrorDict(t_cam_obj=t[0].copy(), code=z[0].copy(), is_good=True, loss=torch.tensor(float(loss[0])),
-                                     **self._posterior_fields(res, 0), **self._prior_fields(res, 0, priors))
+                                     **self._posterior_fields(res, 0), **self._report_fields(res, 0), **self._prior_fields(res, 0, priors))
         return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[0]))
 
     @staticmethod

@@ -479,6 +479,52 @@ int dsp_batch_step_log(dsp_batch* b, int32_t* decision, double* cost, double* la
 int dsp_debug_step_rule(int32_t n, const double* cost, double lambda0, double up, double down, double lambda_min, double lambda_max,
                         int32_t* decision, double* lambda);
 
+/* ---- observation report (optional): which observations disagree with the returned state ---------------------------------------------------
+ * With the report on, a run evaluates every observation once more at the state it RETURNS (x_acc with step control, the frozen state under
+ * the convergence rule) and keeps the values on the device until dsp_batch_report_fetch copies them: a run adds launches, no read-back.
+ * The evaluation is the front of the posterior's pass -- shared with it when the posterior is on, run by the report itself otherwise
+ * (without the Gram launch, which feeds the posterior alone): same sampling, selection rules, prepass, guard and launch forms as an
+ * iteration; status words parked and put back.  dsp_batch_results, _iterations_used, _trace, the step log, posterior records and the
+ * prior's residual are bit for bit what they are with the report off.  Off (initial): the run launches the kernels of a batch that never
+ * had it.  A MEMBER is what the batch iterates over: an object of a joint or pose-only batch, a VIEW of a multi-view batch (in view_off
+ * order, evaluated at T_oc_v).  Arrays are concatenated in member order, exactly as the inputs were given (pts_off / ray_off).
+ *   per surface point   pt_sdf     the decoder value at the transformed point: the residual of compute_sdf_loss (loss.py:22-43)
+ *                       pt_flags   bit 0: the point is alive -- always set in joint and multi-view batches; a pose-only batch: the inlier
+ *                                  filter's mask as the pass (the last evaluation) used it
+ *   per ray (foreground rays first, as uploaded; a pose-only batch has none)
+ *                       ray_depth     d_u of loss.py:100-114, with 1.1 d_max as the background term
+ *                       ray_hit       1 - T_{D-1}: the silhouette probability
+ *                       ray_residual  obs - d_u, UNCLIPPED; obs = the uploaded depth of a foreground ray, 1.1 d_max behind them (optimizer.py:126)
+ *                       ray_counts    3 per ray: in-sphere samples, band samples (-th < sdf < th), kept samples (de_do > 1e-2: the rows this
+ *                                     ray contributed).  The band count is INFORMATIONAL, like dsp_compute_render_loss' m: samples behind a
+ *                                     ray's first solid sample are not decoded where early ray termination or the prepass is on (their
+ *                                     transmittance is exactly 0: they reach neither d_u, the hit probability nor a kept row), and are not
+ *                                     counted in it; with dsp_batch_set_ray_passes(1) and the prepass off it is the reference's.
+ *   per member, 8 doubles   M, V, m, K (pose-only: M = points alive, the others 0) | sum_s = sum (w r)^2 over the member's surface rows with the
+ *                       weights of get_robust_res(., b2) (a pose-only batch: r^2 over its alive points, as optimizer.py:69-72 has no weights) |
+ *                       sum_r = the same over its kept render rows with b1 -- each w r the float32 last column of the row, squared and summed
+ *                       in fp64 | the member's status at the pass (DSP_OBJ_*) | 0 (reserved).  A single-view object's
+ *                       k2 sum_s / M + k1 sum_r / K is the loss at the returned state; any pooling over views is the caller's.
+ * A member that did not end good has NaN in its float rows and sums, zero counts and flags, and its status says why.  A view with fewer
+ * than 10 in-sphere samples at that state has no render term (loss.py:73-74): its ray rows are NaN, its ray counts, K, m and sum_r
+ * are 0 and its status is DSP_OBJ_FEW_SAMPLES; its surface points, which the pooled system does use, are reported (pt_sdf, flags, M, sum_s).
+ * A member left out of the partial re-run after a prepass-guard trip keeps the rows it had, as posterior records do.
+ * Works on joint, pose-only and multi-view batches, with the convergence rule, step control, prior and posterior, in either compute mode
+ * (the low-precision mode's values are that mode's: no accuracy is claimed for them).  The report arrays (5 B per point, 24 B per ray) come
+ * from the handle's pool the first time the report is enabled: DSP_E_NOMEM leaves the report off and the batch usable.  DSP_E_ARG: on
+ * outside {0, 1}.  dsp_batch_report_fetch: any pointer may be NULL; DSP_E_STATE if the last run had no report.  The one-shot calls have
+ * no report.  (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+int dsp_batch_report(dsp_batch* b, int on);                    /* 0 = off (initial) */
+int dsp_batch_report_sizes(dsp_batch* b, int64_t* n_points, int64_t* n_rays, int64_t* n_members);
+int dsp_batch_report_fetch(dsp_batch* b, float* pt_sdf, uint8_t* pt_flags, float* ray_depth, float* ray_hit, float* ray_residual,
+                           int32_t* ray_counts /* n_rays x 3 */, double* member /* n_members x 8 */);
+/* Testing (host only, no device): ONE ray in the scalar statement of the arithmetic (csrc/report_math.h) that the device kernels are built
+ * from.  depths, sdf: n_depth entries (2..64); sdf = the value the occupancy scan reads, NaN = the sample is not in the unit sphere.
+ * out4 = {d_u, 1 - T_{D-1}, obs - d_u unclipped, the clipped residual of the render rows}; counts3 as ray_counts.  depth_obs is read for a
+ * foreground ray only. */
+int dsp_debug_report_ray(int32_t n_depth, const float* depths, const float* sdf /* NaN = not in the sphere */, float th, float depth_obs,
+                         int is_fg, float* out4, int32_t* counts3);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */
@@ -509,8 +555,8 @@ int dsp_batch_debug_start_state(dsp_batch* b, const float* t_obj_cam, const floa
 /* Forensics: iteration e < n_iterations of the following runs samples the rays at depths[(e * n_objects + i) * 64 ..] instead of
  * the depths derived from the pose (n_iterations = 0 turns the schedule off). */
 int dsp_batch_debug_depth_schedule(dsp_batch* b, const float* depths, int32_t n_iterations);
-/* Forensics: the per-sample arrays the LAST iteration of the last run left behind for object obj (with the posterior on, that is the
- * posterior pass: it is then the last linearisation of the last run, at the returned state), expanded to
+/* Forensics: the per-sample arrays the LAST iteration of the last run left behind for object obj (with the posterior or the
+ * observation report on, that is their pass: it is then the last linearisation of the last run, at the returned state), expanded to
  * (n_rays x num_depth_samples) grids: raymask (n_rays; bit j = sample j lies inside the unit sphere), ssdf (the sdf the occupancy
  * scan read: fp32 inside the band, the prepass value or the placeholder 1.0 elsewhere; NaN = not in the sphere), sdeds (de_ds of a kept
  * sample, 0 = not kept, NaN = not in the sphere).  cap = floats available in ssdf / sdeds (>= n_rays * num_depth_samples). */

@@ -115,7 +115,7 @@ def prior_arrays(prior, objs, obs, idx):
 
 
 def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None,
-               step_control=None):
+               step_control=None, report=False):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
@@ -126,7 +126,10 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     prior: None, or the arrays of a level-2 posterior file (ids, status, t_obj_cam, code, Lambda, t_world_cam): prior_arrays;
     stats["prior_chi2"] then holds e^T Lambda e at each observed object's result (NaN: the object failed).
     step_control: None, or (lambda0, up, down, lambda_min, lambda_max) -- Batch.set_step_control; stats["step_decisions"] then holds
-    (accepted, rejected) counted over all observed objects and iterations."""
+    (accepted, rejected) counted over all observed objects and iterations.
+    report: True switches the observation report on (Batch.set_report); stats["report"] then maps "<object id>/<key>" to that object's rows
+    (dsp_slam_amd.observations.object_rows: per-point sdf and alive bits, per-ray depth / hit / residual / counts, per-view sums), as
+    numpy.savez takes them."""
     from dsp_slam_amd import distributed as D
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
@@ -147,6 +150,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     if multiview and step_control is not None:
         raise ValueError("step control does not take multi-view objects")
     steps = [None] * len(shards)
+    reports = [None] * len(shards)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
 
@@ -154,7 +158,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if (tol is not None or posterior is not None or pri is not None or step_control is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None or pri is not None or step_control is not None or report) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -170,7 +174,11 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                     bt.set_prior(pri[0][a:b], pri[1][a:b], pri[2][a:b])
                 if step_control is not None:
                     bt.set_step_control(*step_control)
+                if report:
+                    bt.set_report(True)
                 bt.run()
+                if report:
+                    reports[r] = bt.report()
                 if step_control is not None:
                     dec = bt.step_log()["decision"]
                     steps[r] = (int((dec == 1).sum()), int((dec == 2).sum()))
@@ -230,9 +238,20 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                 records[key][idx[k:k + m]] = pr[key]
             k += m
     prior_chi2 = None if pri is None else np.concatenate([c for c in chi2 if c is not None] + [np.zeros(0)])
+    rows = None
+    if report:
+        from dsp_slam_amd.observations import object_rows
+        rows, k = {}, 0
+        for rp in reports:
+            if rp is None:
+                continue
+            for j in range(len(rp["view_off"]) - 1):
+                for key, val in object_rows(rp, j).items():
+                    rows["%d/%s" % (objs[idx[k]]["id"], key)] = val
+                k += 1
     step_decisions = None if step_control is None else tuple(int(sum(x[k] for x in steps if x is not None)) for k in (0, 1))
     return out, dict(step_decisions=step_decisions, prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
-                     iterations_used=iters, posterior=records)
+                     iterations_used=iters, posterior=records, report=rows)
 
 
 def main():
@@ -253,6 +272,9 @@ def main():
                     help="fuse the records of an earlier run (written with --posterior FILE.npz --posterior-level 2) into this one as a Gaussian prior")
     ap.add_argument("--step-control", type=float, nargs=5, metavar=("L0", "UP", "DOWN", "LMIN", "LMAX"), default=None,
                     help="Levenberg-Marquardt step control: keep a state only if it lowers the loss (conventional: 0 10 0.1 1 inf); off without the flag")
+    ap.add_argument("--report", default=None, metavar="FILE.npz",
+                    help="write every observed object's observation report at its result, keyed '<object id>/<field>': per-point sdf and alive bits, per-ray "
+                         "depth / hit / residual / counts, per-view sums (dsp_slam_amd.observations reads them)")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -267,7 +289,8 @@ def main():
     out, st = reoptimise([d.engine for d in decoders], prm, objs, obs, cfg.optimizer.code_len, compute={"f32": 0, "f16": 1, "bf16": 2}[args.compute],
                          tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum",
                          posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)),
-                         step_control=None if args.step_control is None else tuple(args.step_control))
+                         step_control=None if args.step_control is None else tuple(args.step_control),
+                         report=args.report is not None)
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
@@ -281,6 +304,9 @@ def main():
         print("prior chi2 at the results: median %.3g, max %.3g over %d objects (%d failed)" % (
             float(np.nanmedian(c)) if np.isfinite(c).any() else float("nan"), float(np.nanmax(c)) if np.isfinite(c).any() else float("nan"), c.size,
             int(np.isnan(c).sum())))
+    if st["report"] is not None:
+        np.savez(args.report, **st["report"])
+        print("observation report of %d objects -> %s" % (len({k.split("/")[0] for k in st["report"]}), args.report))
     if st["posterior"] is not None:
         rec = st["posterior"]
         np.savez(args.posterior, **rec)

@@ -318,6 +318,17 @@ struct StepDev {
     int last = 0;               // the run's last iteration: evaluate and decide, apply no step
 };
 
+// Per-observation weights (dsp_batch_observation_weights), all null = off: the run's launches are those of a batch without them.  A weight
+// multiplies the observation's squared residual: H gets sum w J^T J, b gets -sum w J^T r~, and the means divide by the sums of the weights
+// (fp64, fixed order: k_weight_sums) instead of the counts.  A ray of weight 0 is absent: never sampled.
+struct ObsWeightsDev {
+    const float* pt_w = nullptr;    // per surface point, in the order of the inputs (ObjConst::pts_off)
+    const float* ray_w = nullptr;   // per ray (ObjConst::ray_off)
+    float* jw = nullptr;            // per jacobian row, render rows only (from ObjConst::jren_off): the weight of the row's ray, written by the row writers
+    double* sums = nullptr;         // 2 per member: sum of w over the (alive) surface points, over the kept render rows
+    double* gsums = nullptr;        // multi-view batches, 2 per member, written at the leaders: the group's pooled sums (k_group_reduce)
+};
+
 // kernels_mlp / kernels_gn launchers
 size_t mlp_lds_bytes(int mode);
 void launch_code_bias(const float* codew, const float* b0, const float* blat, const float* codes, int code_stride, float* out, int n_obj, hipStream_t s);
@@ -335,7 +346,8 @@ hipError_t launch_mlp_lpj(int which, bool bf16, const LpjArgs& args, int n_block
 // summary: the run's counter words, zeroed here (summary_words of them)
 void launch_init_state(ObjState* st, const float* t, const float* codes, const float* scale, const float* depths /*optional B x 64*/, int B, int D, int pose_only,
                        const LpDeltaTab& lp, const unsigned char* run_mask, unsigned* summary, int summary_words, hipStream_t s);
-void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s);
+void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s,
+                         const float* ray_w = nullptr);   // ray_w (observation weights, optional): a ray of weight 0 gets an empty mask
 void launch_scan_rays(const ObjConst* oc, ObjState* st, const int* cnt, int* off, int which, int B, hipStream_t s);
 void launch_sample_write(const ObjConst* oc, const ObjState* st, const float* rays, const unsigned long long* m, const int* off, float4* spts,
                          float* ssdf, unsigned char* alive, int D, int maxR, int B, hipStream_t s);
@@ -352,18 +364,20 @@ void launch_band_select(const ObjConst* oc, ObjState* st, const unsigned long lo
 // surface, band = count + scan + write, render tail = scan + sum_m + render_write (behind k_render_scan): list segments from running counters
 // (ObjState::V / ::P) instead of scans; kept rows stay in ray-major order.  See gn_kernels.hip.
 void launch_front_wave(const ObjConst* oc, ObjState* st, const float* rays, const float* pts, unsigned long long* raymask, int* raycnt, int* rayoff,
-                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s);
+                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s,
+                       const float* ray_w = nullptr);
 void launch_band_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th, unsigned guard_salt,
                       int* plist, const float4* spts, float4* jpts, int* srow, int maxR, int B, hipStream_t s);   // jpts / srow: speculative band rows (or null)
 void launch_render_tail_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float4* spts, const float* sdeds,
                              const float* ray_res, const int* kcnt, const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow, int maxR, int B,
-                             hipStream_t s);
+                             hipStream_t s, const float* ray_w = nullptr, float* jw = nullptr);   // ray_w / jw (both or neither): every kept row's weight
 void launch_prepass_audit(const ObjConst* oc, const ObjState* st, const float* ssdf, const float* saudit, float th, unsigned* out,
                           int B, hipStream_t s);
 void launch_render_scan(const ObjConst* oc, ObjState* st, const unsigned long long* m, const int* off, const float* ssdf, const float* depth,
                         float* sdeds, float* ray_res, int* kcnt, int* mcnt, int D, float th, int maxR, int B, hipStream_t s);
 void launch_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff, const float4* spts,
-                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s);
+                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s,
+                         const float* ray_w = nullptr, float* jw = nullptr);
 // one front-to-back forward pass: fixed depth-index range [j0, j1) (hint == nullptr), or per-ray adaptive ranges where
 // j0 = margin added to the hint in pass 0 and j1 = step of the middle passes
 struct PassSpec {
@@ -379,7 +393,8 @@ void launch_pass_update(const ObjConst* oc, const ObjState* st, const unsigned l
                         const float* ssdf, float th, int use_lp_delta, const PassSpec& ps, int maxR, int B, hipStream_t s);   // use_lp_delta: a ray stops at sdf <= -(th + st[b].lp_delta)
 void launch_sum_m(const ObjConst* oc, ObjState* st, const int* mcnt, int B, hipStream_t s);
 void launch_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow,
-                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s);
+                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s,
+                 const ObsWeightsDev* ow = nullptr);   // ow: the weighted instantiation, and k_weight_sums behind it (nullptr: the kernel without weights, alone)
 void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow, int term, float* rows,
                   int cap, hipStream_t s);   // jrow (optional): render row i takes its gradient from jgrad row jrow[i]
 // grp / gmk (both or neither; nullptr = every member is an object of its own): multi-view groups -- the members' Gram sums are pooled at the
@@ -387,7 +402,7 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
                   hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr, const PriorDev* prior = nullptr,
-                  const StepDev* step = nullptr);    // step: Levenberg-Marquardt step control, nullptr = off (the kernel without it)   // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+                  const StepDev* step = nullptr, const ObsWeightsDev* ow = nullptr);    // ow: the means divide by the weight sums   // step: Levenberg-Marquardt step control, nullptr = off (the kernel without it)   // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
 // the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
 // -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
@@ -400,7 +415,7 @@ constexpr int POSTERIOR_REC_L2 = POSTERIOR_REC_L1 + 71 * 71 + 71 + (16 + CODE_LE
 void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
                       const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr,
-                      const PriorDev* prior = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
+                      const PriorDev* prior = nullptr, const ObsWeightsDev* ow = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
 // observation report (dsp_batch_report): the device arrays of one batch, in the order of the inputs -- points by pts_off, rays by ray_off,
 // 8 doubles per member.  launch_report runs k_report_rays / k_report_points / k_report_members behind the front of the pass at the
 // returned state; park (optional): k_report_members puts the parked status words back (the posterior is off: nobody else will).
@@ -416,7 +431,7 @@ struct ReportDev {
 };
 void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
                    const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
-                   int maxM, int B, hipStream_t s);
+                   int maxM, int B, hipStream_t s, const ObsWeightsDev* ow = nullptr);   // ow: sum_s / sum_r are the weighted sums; a ray of weight 0 reads as absent
 void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3);
 // the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass 1: e and chi2 at the returned
 // state instead; 2 (launch_solve with step control): the terms, and chi2 at the current state in the record's chi2 slot

@@ -181,11 +181,12 @@ __device__ __forceinline__ unsigned id_hash(unsigned id) { return (id * 26544357
 // ------------------------------------------------------------------------------------------------
 // ray sampling: in-sphere mask + count per ray  (loss.py:60-70)
 // ------------------------------------------------------------------------------------------------
+// (ray_w, optional: the caller's observation weights -- a ray of weight 0 is absent: an empty mask, no sample, nothing in V or the checksum)
 __device__ __forceinline__ void sample_count_ray(const ObjConst& c, ObjState* st, int b, const float* rays, unsigned long long* raymask,
-                                                 int* raycnt, int n_depth, int r) {
+                                                 int* raycnt, int n_depth, int r, const float* ray_w) {
     const ObjState& s = st[b];
     unsigned long long mask = 0ull;
-    if (s.status == DSP_STATUS_GOOD) {
+    if (s.status == DSP_STATUS_GOOD && !(ray_w && ray_w[c.ray_off + r] == 0.f)) {
         const float* d3 = rays + 3 * (size_t)(c.ray_off + r);
         const float dx = d3[0], dy = d3[1], dz = d3[2];
         for (int j = 0; j < n_depth; ++j) {
@@ -203,12 +204,12 @@ __device__ __forceinline__ void sample_count_ray(const ObjConst& c, ObjState* st
 }
 
 __global__ void k_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* raymask,
-                               int* raycnt, int n_depth) {
+                               int* raycnt, int n_depth, const float* ray_w) {
     const int b = blockIdx.y;
     const ObjConst c = oc[b];
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= c.n_rays) return;
-    sample_count_ray(c, st, b, rays, raymask, raycnt, n_depth, r);
+    sample_count_ray(c, st, b, rays, raymask, raycnt, n_depth, r, ray_w);
 }
 
 // exclusive scan of per-ray counts inside each object (one workgroup per object)
@@ -747,7 +748,7 @@ __global__ __launch_bounds__(256) void k_render_scan(const ObjConst* oc, ObjStat
 // A member that is not good at the pass, or has < 10 in-sphere samples there (no render term: loss.py:73-74), gets NaN and zero counts.
 __global__ __launch_bounds__(256) void k_report_rays(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff,
                                                      const float* ssdf, const float* depth_fg, int n_depth, float th, float* ray_depth, float* ray_hit,
-                                                     float* ray_residual, int* ray_counts) {
+                                                     float* ray_residual, int* ray_counts, const float* ray_w) {
     const int b = blockIdx.y;
     const ObjConst c = oc[b];
     const int lane = threadIdx.x & 63;
@@ -756,7 +757,8 @@ __global__ __launch_bounds__(256) void k_report_rays(const ObjConst* oc, const O
     const ObjState& s = st[b];
     if (s.status == DSP_STATUS_SKIP) return;
     const int gr = c.ray_off + r;
-    if (s.status != DSP_STATUS_GOOD || s.V < 10) {
+    // (observation weights: a ray of weight 0 is absent -- the rows of a member without a render term)
+    if (s.status != DSP_STATUS_GOOD || s.V < 10 || (ray_w && ray_w[gr] == 0.f)) {
         if (lane == 0) {
             ray_depth[gr] = ray_hit[gr] = ray_residual[gr] = __int_as_float(0x7fc00000);
             ray_counts[3 * gr] = ray_counts[3 * gr + 1] = ray_counts[3 * gr + 2] = 0;
@@ -798,7 +800,8 @@ __global__ __launch_bounds__(256) void k_report_points(const ObjConst* oc, const
 // fp64: every thread a strided partial sum, then a fixed tree.  park (optional): the member's parked status word goes back afterwards --
 // what k_posterior does when the posterior is on.
 __global__ __launch_bounds__(256) void k_report_members(const ObjConst* oc, ObjState* st, const float2* jaux, const float* jgrad, const unsigned char* alive,
-                                                        float b_sdf, float b_render, int robust, int pose_only, const int* park, double* out) {
+                                                        float b_sdf, float b_render, int robust, int pose_only, const int* park, double* out,
+                                                        const float* pt_w, const float* jw) {
     __shared__ double part[2][256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const ObjConst c = oc[b];
@@ -814,12 +817,16 @@ __global__ __launch_bounds__(256) void k_report_members(const ObjConst* oc, ObjS
             const int idx = c.jsdf_off + i;
             if (alive && !alive[idx]) continue;
             const float r = jgrad[(size_t)idx * GRAD_STRIDE + 67];
-            const double wr = (double)(robust ? report_math::robust_residual(r, b_sdf) : r);
+            float wf = robust ? report_math::robust_residual(r, b_sdf) : r;
+            if (pt_w) { const float w = pt_w[c.pts_off + i]; if (w == 0.f) continue; wf = __fmul_rn(__fsqrt_rn(w), wf); }     // k_gram<true>'s last column
+            const double wr = (double)wf;
             acc_s = __dadd_rn(acc_s, __dmul_rn(wr, wr));
         }
         for (int i = tid; i < K; i += 256) {
             const float r = jaux[c.jren_off + i].y;
-            const double wr = (double)(robust ? report_math::robust_residual(r, b_render) : r);
+            float wf = robust ? report_math::robust_residual(r, b_render) : r;
+            if (jw) wf = __fmul_rn(__fsqrt_rn(jw[c.jren_off + i]), wf);
+            const double wr = (double)wf;
             acc_r = __dadd_rn(acc_r, __dmul_rn(wr, wr));
         }
     }
@@ -848,7 +855,8 @@ __global__ __launch_bounds__(256) void k_report_members(const ObjConst* oc, ObjS
 // the rows of the rays in front (koff).  One WAVE per ray, lane = position in the ray's compact sample run: one coalesced load finds the kept
 // ones, a ballot places them.
 __global__ __launch_bounds__(256) void k_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff,
-                               const float4* spts, const float* sdeds, const float* ray_res, float4* jpts, float2* jaux) {
+                               const float4* spts, const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, const float* ray_w,
+                               float* jw) {
     const int b = blockIdx.y;
     const ObjConst c = oc[b];
     const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
@@ -867,6 +875,7 @@ __global__ __launch_bounds__(256) void k_render_write(const ObjConst* oc, const 
     p.w = __int_as_float(base + k);   // compact sample index: where the forward launch left this sample's sdf and relu masks
     jpts[dst] = p;
     jaux[dst] = make_float2(dv, ray_res[gr]);
+    if (jw) jw[dst] = ray_w[gr];      // observation weights: the row carries the weight of its ray
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -906,7 +915,8 @@ __device__ __forceinline__ int wave_segment(int* counter, int* s_cnt, int* s_bas
 // iteration; the "< 10 samples" rule of loss.py:73-74 is applied by the tile builder that follows, k_build_tiles apply_few)
 __global__ __launch_bounds__(WAVE_THREADS) void k_front_wave(const ObjConst* oc, ObjState* st, const float* __restrict__ rays, const float* pts,
                                                              unsigned long long* raymask, int* raycnt, int* rayoff, float4* spts, float* ssdf,
-                                                             unsigned char* alive, float4* jpts, float2* jaux, int n_depth, int n_ray_blocks) {
+                                                             unsigned char* alive, float4* jpts, float2* jaux, int n_depth, int n_ray_blocks,
+                                                             const float* ray_w) {
     __shared__ int s_cnt[WAVE_RAYS], s_base;
     __shared__ unsigned s_hash[WAVE_RAYS];
     const int b = blockIdx.y;
@@ -919,7 +929,8 @@ __global__ __launch_bounds__(WAVE_THREADS) void k_front_wave(const ObjConst* oc,
     }
     if ((int)blockIdx.x * WAVE_RAYS >= c.n_rays) return;       // workgroup-uniform
     const int r = blockIdx.x * WAVE_RAYS + wave;
-    const bool live = r < c.n_rays && st[b].status == DSP_STATUS_GOOD;
+    bool live = r < c.n_rays && st[b].status == DSP_STATUS_GOOD;
+    if (ray_w && live) live = ray_w[c.ray_off + r] != 0.f;      // observation weights: a ray of weight 0 is absent (wave-uniform)
     bool in = false;
     float3 p = make_float3(0.f, 0.f, 0.f);
     if (live && lane < n_depth) {
@@ -1006,7 +1017,8 @@ constexpr int TAIL_RAYS = 64;
 
 __global__ __launch_bounds__(WAVE_THREADS) void k_render_tail_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff,
                                                                    const float4* spts, const float* sdeds, const float* ray_res, const int* kcnt,
-                                                                   const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow) {
+                                                                   const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow,
+                                                                   const float* ray_w, float* jw) {
     __shared__ int part[3][WAVE_RAYS];
     __shared__ int s_koff[TAIL_RAYS];
     const int b = blockIdx.y;
@@ -1059,6 +1071,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void k_render_tail_wave(const ObjCons
             p.w = __int_as_float(sidx);       // compact sample index: where the forward launch left this sample's sdf and relu masks
             jpts[dst] = p;
             jaux[dst] = make_float2(dv, ray_res[gr]);
+            if (jw) jw[dst] = ray_w[gr];      // observation weights: the row carries the weight of its ray
             if (jrow) jrow[dst] = srow[sidx]; // speculative band rows: this row's gradient already sits in jgrad row srow[sample]
         }
     }
@@ -1104,9 +1117,15 @@ constexpr int GRAM_PTS = 32;    // granularity of a slice's share of the rows (p
 constexpr int GRAM_SUB = 4;     // row groups of GRAM_PTS staged per barrier pair: the loads of all of them are in flight together
 constexpr int JLD = 73;         // LDS row stride (odd: conflict-free column access)
 
+// WEIGHTED (dsp_batch_observation_weights): every staged value of a row -- the 71 jacobian columns and the robust residual, behind
+// robust_residual -- is multiplied by the correctly rounded fp32 square root of the row's weight (a surface row: pt_w of its point; a render
+// row: jw, the weight of its ray), so that the Gram sums are sum w J^T J, sum w J^T r~ and sum w r~^2.  A row of weight 0 is a zero row, like
+// a point the inlier filter dropped.  x * 1.0f is exact: with unit weights the staged bits are those of WEIGHTED = false, which is the code
+// of every run without weights (a template argument: nothing of it is compiled into that instantiation).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux,
                                               const float* jgrad, const int* jrow, const unsigned char* alive, float* partials, int n_slices,
-                                              float b_sdf, float b_render, int robust) {
+                                              float b_sdf, float b_render, int robust, const float* pt_w, const float* jw) {
     __shared__ float J[GRAM_SUB * GRAM_PTS * JLD];
     const int slice = blockIdx.x, b = blockIdx.y, term = blockIdx.z;
     const ObjConst c = oc[b];
@@ -1135,10 +1154,19 @@ __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState
             float4 ga[GRAM_SUB], gb[GRAM_SUB], gx[GRAM_SUB], pp[GRAM_SUB];
             float2 aux[GRAM_SUB];
             bool live[GRAM_SUB];
+            [[maybe_unused]] float sw[GRAM_SUB];
 #pragma unroll
             for (int q = 0; q < GRAM_SUB; ++q) {
                 const int r = r0 + GRAM_PTS * q;
                 live[q] = r < np && (alive == nullptr || term != 0 || alive[off + p0 + r]);
+                if constexpr (WEIGHTED) {
+                    sw[q] = 0.f;
+                    if (live[q]) {
+                        const float w = (term == 0) ? pt_w[c.pts_off + p0 + r] : jw[off + p0 + r];
+                        live[q] = w != 0.f;
+                        sw[q] = __fsqrt_rn(w);
+                    }
+                }
                 ga[q] = gb[q] = gx[q] = pp[q] = make_float4(0.f, 0.f, 0.f, 0.f);
                 aux[q] = make_float2(0.f, 0.f);
                 if (live[q]) {
@@ -1164,6 +1192,10 @@ __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState
                     const float sc = aux[q].x;                                    // de_ds (render) or 1 (sdf)
                     rc[0] = __fmul_rn(sc, ga[q].x); rc[1] = __fmul_rn(sc, ga[q].y); rc[2] = __fmul_rn(sc, ga[q].z); rc[3] = __fmul_rn(sc, ga[q].w);
                     rc[4] = __fmul_rn(sc, gb[q].x); rc[5] = __fmul_rn(sc, gb[q].y); rc[6] = __fmul_rn(sc, gb[q].z); rc[7] = __fmul_rn(sc, gb[q].w);
+                    if constexpr (WEIGHTED) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) rc[i] = __fmul_rn(sw[q], rc[i]);
+                    }
                     if (part == 0) {
                         const float4 p = pp[q];
                         const float res = (term == 0) ? gx[q].w : aux[q].y;   // sdf term: residual is the sdf itself (loss.py:34,43)
@@ -1176,6 +1208,11 @@ __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState
                         row[6] = __fadd_rn(__fadd_rn(__fmul_rn(p.x, d0), __fmul_rn(p.y, d1)), __fmul_rn(p.z, d2));
                         // huber_norm_weights: w = sqrt(rho)/|r|, only the residual is reweighted (loss_utils.py:236-265)
                         row[71] = robust ? report_math::robust_residual(res, hb) : res;
+                        if constexpr (WEIGHTED) {
+#pragma unroll
+                            for (int i = 0; i < 7; ++i) row[i] = __fmul_rn(sw[q], row[i]);
+                            row[71] = __fmul_rn(sw[q], row[71]);
+                        }
                     }
                 } else {
 #pragma unroll
@@ -1213,6 +1250,34 @@ __global__ __launch_bounds__(256) void k_gram(const ObjConst* oc, const ObjState
 #pragma unroll
             for (int j = 0; j < 6; ++j) out[(bi + i) * 72 + bj + j] = acc[i][j];
     }
+}
+
+// Observation weights: the normalisers that take the place of M (pose-only: the points alive) and K -- per member, sums[2 b] = sum of w over
+// its (alive) surface points, sums[2 b + 1] = sum of w over its K kept render rows, each weight widened to fp64 first.  One workgroup per
+// member, behind k_gram: every thread a strided partial sum, then the fixed LDS tree of k_report_members -- the same bits in every run,
+// no atomics.  Sums of ones are exact: with unit weights the results are (double)M and (double)K.
+__global__ __launch_bounds__(256) void k_weight_sums(const ObjConst* oc, const ObjState* st, const float* pt_w, const float* jw, const unsigned char* alive,
+                                                     int pose_only, double* sums) {
+    __shared__ double part[2][256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const ObjConst c = oc[b];
+    const bool good = st[b].status == DSP_STATUS_GOOD;
+    const int K = (good && !pose_only) ? st[b].K : 0;
+    double acc_p = 0.0, acc_k = 0.0;
+    if (good) {
+        for (int i = tid; i < c.n_pts; i += 256) {
+            if (alive && !alive[c.jsdf_off + i]) continue;
+            acc_p = __dadd_rn(acc_p, (double)pt_w[c.pts_off + i]);
+        }
+        for (int i = tid; i < K; i += 256) acc_k = __dadd_rn(acc_k, (double)jw[c.jren_off + i]);
+    }
+    part[0][tid] = acc_p; part[1][tid] = acc_k;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (tid < d) { part[0][tid] = __dadd_rn(part[0][tid], part[0][tid + d]); part[1][tid] = __dadd_rn(part[1][tid], part[1][tid + d]); }
+        __syncthreads();
+    }
+    if (tid == 0) { sums[2 * b] = part[0][0]; sums[2 * b + 1] = part[1][0]; }
 }
 
 // J rows to memory, for the stand-alone compute_sdf_loss / compute_render_loss entry points
@@ -1355,8 +1420,9 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const ObjState* st, const f
 // FEW when no view reached 10 in-sphere samples (every compute_render_loss returned None, loss.py:73-74), a member's failure (a singular
 // pose) otherwise; M == 0, K == 0 and a NaN loss are k_solve's tests, on the pooled numbers.  With a trace, the non-leader members' rows
 // get their own state, V, m, K, checksums and depths (the leader's row is k_solve's).
+// wsums / gwsums (observation weights, both or neither): the members' weight sums (k_weight_sums) are pooled like M and K, in member order.
 __global__ __launch_bounds__(256) void k_group_reduce(const GroupEnt* grp, const ObjConst* oc, ObjState* st, double* gsum, int* gmk, int iter,
-                                                      float* trace, int n_obj) {
+                                                      float* trace, int n_obj, const double* wsums, double* gwsums) {
     const int b = blockIdx.y, term = blockIdx.z, tid = threadIdx.x;
     const GroupEnt g = grp[b];
     if (g.leader != b) return;
@@ -1377,16 +1443,19 @@ __global__ __launch_bounds__(256) void k_group_reduce(const GroupEnt* grp, const
     if (blockIdx.x != 0 || term != 0) return;
     if (tid == 0) {
         int M = 0, K = 0, bad = DSP_STATUS_GOOD;
+        double Mw = 0.0, Kw = 0.0;
         bool any = false;
         for (int v = 0; v < g.n_members; ++v) {
             const ObjState& s = st[b + v];
             if (s.status != DSP_STATUS_GOOD) { if (bad == DSP_STATUS_GOOD) bad = s.status; continue; }
             M += oc[b + v].n_pts;
             K += s.K;
+            if (wsums) { Mw = __dadd_rn(Mw, wsums[2 * (b + v)]); Kw = __dadd_rn(Kw, wsums[2 * (b + v) + 1]); }
             any = any || s.V >= 10;
         }
         gmk[2 * b] = M;
         gmk[2 * b + 1] = K;
+        if (wsums) { gwsums[2 * b] = Mw; gwsums[2 * b + 1] = Kw; }
         if (!any) st[b].status = DSP_STATUS_FEW;
         else if (bad != DSP_STATUS_GOOD) st[b].status = bad;
     }
@@ -1552,7 +1621,11 @@ template <bool GROUPS, bool STOP, bool PRIOR, bool STEP>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int iter,
                                                          const float* codew, const float* cb0, const float* cblat, float* cbias,
                                                float* trace /*nullable*/, const float* depths_next /*nullable: forensics*/, int n_obj,
-                                               const GroupEnt* grp, const int* gmk, StopRule stop, PriorDev pr, StepDev sd) {
+                                               const GroupEnt* grp, const int* gmk, StopRule stop, PriorDev pr, StepDev sd, const double* wn) {
+    // wn (observation weights; nullptr = off): 2 doubles per member, the sums of the caller's weights that take the place of M (pose-only: Ma)
+    // and K as the divisors of the means -- the member's own (k_weight_sums) or, GROUPS, the group's pooled ones (k_group_reduce).  The
+    // counts stay counts.  (double)M is what the divisions below widen M to anyway, and (float)(double)M == (float)M: with wn == nullptr
+    // every result bit is that of the kernel before it had the argument; with unit weights wn holds (double)M and (double)K exactly.
     static_assert(!(STEP && GROUPS), "step control: joint batches without groups only");
     __shared__ double A[NS1][NS1 + 1];          // [H | b] in rows 0..n-1 (b = column n); b is also kept as ROW n (rows 64 .. 71 are one register of the elimination)
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -1579,6 +1652,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     auto gram = [=](int term, int idx) -> double { return (term ? G1p : G0p)[idx]; };
     int M = c.n_pts;
     if constexpr (GROUPS) M = gmk[2 * b];
+    const int n_alive = s.n_alive;
+    const double Mw = wn ? wn[2 * b] : (double)(prm.pose_only && n_alive >= 0 ? n_alive : M);
+    const double Kw = wn ? wn[2 * b + 1] : (double)K;
     const int pd = prm.pose_only ? 6 : 7;
     const int n = prm.pose_only ? 6 : NSOLVE;
     // thread (tr, tc) fills column tc of rows tr, tr+12, ... of the joint system: its Gram loads
@@ -1625,9 +1701,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
     if (tid >= 64 && tid < 64 + CODE_LEN) s_code0[tid - 64] = park;
     if (!prm.pose_only) {
         // losses (optimizer.py:134-155): mean of robust residual^2; an empty set gives NaN in the reference
-        if (M == 0 || K == 0) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }
-        const float sdf_loss = (float)g_loss0 / (float)M;
-        const float ren_loss = (float)g_loss1 / (float)K;
+        if (Mw == 0.0 || Kw == 0.0) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }
+        const float sdf_loss = (float)g_loss0 / (float)Mw;
+        const float ren_loss = (float)g_loss1 / (float)Kw;
         if (isnan(sdf_loss) || isnan(ren_loss)) { if (tid == 0) s.status = DSP_STATUS_NAN; return; }
         if (tid == 0) s.loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
         if constexpr (STEP) sc_loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
@@ -1636,7 +1712,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         // only entries 3 and 5 of the prior's jacobian are non-zero; selects instead of a run-time index keep it out of scratch
         const float jrot3 = jrot[3], jrot5 = jrot[5];
         auto jr = [=](int i) { return i == 3 ? jrot3 : (i == 5 ? jrot5 : 0.f); };
-        const double w_s = (double)prm.k2 / (double)M, w_r = (double)prm.k1 / (double)K;
+        const double w_s = (double)prm.k2 / Mw, w_r = (double)prm.k1 / Kw;
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
             const int i = tr0 + RG * q;
@@ -1663,8 +1739,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
         }
     } else {
         // pose-only (optimizer.py:68-72): H = J6^T J6 / M + 1e-2 I, b = -J6^T r / M with the raw residual
-        const int Ma = (s.n_alive >= 0) ? s.n_alive : M;
-        if (Ma == 0) {      // no point (left): H = J^T J / 0 is NaN in the reference; the trace still records the count
+        const double Ma = Mw;
+        if (Ma == 0.0) {      // no point (left): H = J^T J / 0 is NaN in the reference; the trace still records the count
             if (tid == 0) {
                 s.status = DSP_STATUS_NAN;
                 if (trace) trace[((size_t)iter * n_obj + b) * TRACE_STRIDE + NSOLVE * NSOLVE + 2 * NSOLVE + 82] = 0.f;
@@ -1675,11 +1751,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(const ObjConst* oc, Obj
             const int i = e / (n + 1), j = e % (n + 1);
             double v;
             if (j < n) {
-                v = gram(0, i * 72 + j) / (double)Ma;
+                v = gram(0, i * 72 + j) / Ma;
                 if constexpr (PRIOR) { if (pr_on) v += exb[e]; }
                 if (i == j) v += 1e-2;
             } else {
-                v = -gram(0, i * 72 + 71) / (double)Ma;
+                v = -gram(0, i * 72 + 71) / Ma;
                 if constexpr (PRIOR) { if (pr_on) v += exb[e]; }
             }
             A[i][j] = v;
@@ -2004,7 +2080,8 @@ constexpr int POST_THREADS = 1024;
 // PRIOR (dsp_batch_prior): Lambda and g include the prior's block, added where k_solve<.., true> adds it.
 template <bool GROUPS, bool PRIOR>
 __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, ObjState* st, const double* gsum, GnParamsDev prm, int weights, int level,
-                                                            const int* park, const GroupEnt* grp, const int* gmk, double* rec, int rec_stride, PriorDev pr) {
+                                                            const int* park, const GroupEnt* grp, const int* gmk, double* rec, int rec_stride, PriorDev pr,
+                                                            const double* wn) {      // wn: the weight sums that divide the means, as in k_solve (nullptr = off)
     __shared__ double A[NSOLVE][NSOLVE + 1];
     __shared__ double s_c[NSOLVE + 1], s_d0[NSOLVE + 1];
     __shared__ int s_sing;
@@ -2030,18 +2107,19 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
         for (int v = 0; v < n_mem; ++v) if (st[b + v].status == DSP_STATUS_GOOD) V += st[b + v].V;
     }
     if (prm.pose_only) { M = (s.n_alive >= 0) ? s.n_alive : M; K = 0; V = 0; }
+    const double Mw = wn ? wn[2 * b] : (double)M, Kw = wn ? wn[2 * b + 1] : (double)K;      // the record's M, V, K stay counts
     const double* G0p = gsum + ((size_t)b * 2 + 0) * (72 * 72);
     const double* G1p = gsum + ((size_t)b * 2 + 1) * (72 * 72);
     // status of the record; the loss at x* in k_solve's float32 arithmetic
     int pstat = 0;
     float loss = 0.f;
     if (status != DSP_STATUS_GOOD) pstat = 1;
-    else if (prm.pose_only) { if (M == 0) pstat = 1; }
-    else if (M == 0 || K == 0) pstat = 1;
+    else if (prm.pose_only) { if (Mw == 0.0) pstat = 1; }
+    else if (Mw == 0.0 || Kw == 0.0) pstat = 1;
     else {
         const double g_loss0 = G0p[71 * 72 + 71], g_loss1 = G1p[71 * 72 + 71];
-        const float sdf_loss = (float)g_loss0 / (float)M;
-        const float ren_loss = (float)g_loss1 / (float)K;
+        const float sdf_loss = (float)g_loss0 / (float)Mw;
+        const float ren_loss = (float)g_loss1 / (float)Kw;
         if (isnan(sdf_loss) || isnan(ren_loss)) pstat = 1;
         else loss = prm.k1 * ren_loss + prm.k2 * sdf_loss;
     }
@@ -2070,8 +2148,8 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
         float jrot[7];
         rotation_prior(pr_tco, s.scale, jrot, res_rot);
         jrot3 = jrot[3]; jrot5 = jrot[5];
-        w_s = weights ? (double)prm.k2 : (double)prm.k2 / (double)M;
-        w_r = weights ? (double)prm.k1 : (double)prm.k1 / (double)K;
+        w_s = weights ? (double)prm.k2 : (double)prm.k2 / Mw;
+        w_r = weights ? (double)prm.k1 : (double)prm.k1 / Kw;
     }
     auto jr = [=](int i) { return i == 3 ? jrot3 : (i == 5 ? jrot5 : 0.f); };
     [[maybe_unused]] bool pr_on = false;
@@ -2086,7 +2164,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
     auto lam = [&](int i, int j) -> double {
         if (prm.pose_only) {
             double v = G0p[i * 72 + j];
-            if (!weights) v = v / (double)M;
+            if (!weights) v = v / Mw;
             if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + j]; }
             return v;
         }
@@ -2124,7 +2202,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_posterior(const ObjConst* oc, 
                 A[j][i] = v;
             } else {
                 double v = -G0p[i * 72 + 71];
-                if (!weights) v = v / (double)M;
+                if (!weights) v = v / Mw;
                 if constexpr (PRIOR) { if (pr_on) v += exb[i * xs + xs - 1]; }
                 s_c[i] = v;
             }
@@ -2291,8 +2369,9 @@ void launch_init_state(ObjState* st, const float* t, const float* codes, const f
                        const LpDeltaTab& lp, const unsigned char* run_mask, unsigned* summary, int summary_words, hipStream_t s) {
     hipLaunchKernelGGL(k_init_state, dim3((B + 63) / 64), dim3(64), 0, s, st, t, codes, scale, depths, B, D, pose_only, lp, run_mask, summary, summary_words);
 }
-void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_sample_count, GRID2(maxR, B), dim3(256), 0, s, oc, st, rays, m, c, D);
+void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s,
+                         const float* ray_w) {
+    hipLaunchKernelGGL(k_sample_count, GRID2(maxR, B), dim3(256), 0, s, oc, st, rays, m, c, D, ray_w);
 }
 void launch_scan_rays(const ObjConst* oc, ObjState* st, const int* cnt, int* off, int which, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_scan_rays, dim3(B), dim3(256), 0, s, oc, st, cnt, off, which);
@@ -2327,10 +2406,11 @@ void launch_prepass_audit(const ObjConst* oc, const ObjState* st, const float* s
     hipLaunchKernelGGL(k_prepass_audit, dim3(64, B), dim3(256), 0, s, oc, st, ssdf, saudit, th, out);
 }
 void launch_front_wave(const ObjConst* oc, ObjState* st, const float* rays, const float* pts, unsigned long long* raymask, int* raycnt, int* rayoff,
-                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s) {
+                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s,
+                       const float* ray_w) {
     const int nrb = std::max(1, (maxR + WAVE_RAYS - 1) / WAVE_RAYS), nsb = (maxM + WAVE_THREADS - 1) / WAVE_THREADS;
     hipLaunchKernelGGL(k_front_wave, dim3((unsigned)(nrb + nsb), (unsigned)B), dim3(WAVE_THREADS), 0, s, oc, st, rays, pts, raymask, raycnt, rayoff, spts, ssdf, alive,
-                       jpts, jaux, D, nrb);
+                       jpts, jaux, D, nrb, ray_w);
 }
 void launch_band_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th, unsigned guard_salt,
                       int* plist, const float4* spts, float4* jpts, int* srow, int maxR, int B, hipStream_t s) {
@@ -2339,9 +2419,9 @@ void launch_band_wave(const ObjConst* oc, ObjState* st, const unsigned long long
 }
 void launch_render_tail_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float4* spts, const float* sdeds,
                              const float* ray_res, const int* kcnt, const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow, int maxR, int B,
-                             hipStream_t s) {
+                             hipStream_t s, const float* ray_w, float* jw) {
     hipLaunchKernelGGL(k_render_tail_wave, dim3((unsigned)std::max(1, (maxR + TAIL_RAYS - 1) / TAIL_RAYS), (unsigned)B), dim3(WAVE_THREADS), 0, s, oc, st, raymask,
-                       rayoff, spts, sdeds, ray_res, kcnt, mcnt, jpts, jaux, srow, jrow);
+                       rayoff, spts, sdeds, ray_res, kcnt, mcnt, jpts, jaux, srow, jrow, ray_w, jw);
 }
 void launch_surface(const ObjConst* oc, const ObjState* st, const float* pts, float4* jpts, float2* jaux, int maxM, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_surface, GRID2(maxM, B), dim3(256), 0, s, oc, st, pts, jpts, jaux);
@@ -2360,29 +2440,37 @@ void launch_render_scan(const ObjConst* oc, ObjState* st, const unsigned long lo
 }
 void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
                    const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
-                   int maxM, int B, hipStream_t s) {
+                   int maxM, int B, hipStream_t s, const ObsWeightsDev* ow) {
     if (!prm.pose_only && maxR > 0)
         hipLaunchKernelGGL(k_report_rays, dim3((unsigned)((maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, (const ObjState*)st, raymask, rayoff, ssdf, depth_fg,
-                           prm.n_depth, prm.cut_off, rp.ray_depth, rp.ray_hit, rp.ray_residual, rp.ray_counts);     // one wave per ray
+                           prm.n_depth, prm.cut_off, rp.ray_depth, rp.ray_hit, rp.ray_residual, rp.ray_counts, ow ? ow->ray_w : nullptr);     // one wave per ray
     if (maxM > 0)
         hipLaunchKernelGGL(k_report_points, GRID2(maxM, B), dim3(256), 0, s, oc, (const ObjState*)st, jgrad, alive, rp.pt_sdf, rp.pt_flags);
     hipLaunchKernelGGL(k_report_members, dim3(B), dim3(256), 0, s, oc, st, jaux, jgrad, alive, prm.b2, prm.b1, prm.pose_only ? 0 : 1, prm.pose_only, park,
-                       rp.member);
+                       rp.member, ow ? ow->pt_w : nullptr, (ow && !prm.pose_only) ? (const float*)ow->jw : nullptr);
 }
 void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3) {
     report_math::ray(n_depth, depths, sdf, th, depth_obs, is_fg, out4, counts3);
 }
 void launch_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff, const float4* spts,
-                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s) {
+                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s, const float* ray_w, float* jw) {
     hipLaunchKernelGGL(k_render_write, dim3((unsigned)std::max(1, (maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, st, raycnt, rayoff, koff, spts, sdeds, ray_res,
-                       jpts, jaux);     // one wave per ray
+                       jpts, jaux, ray_w, jw);     // one wave per ray
 }
 void launch_sum_m(const ObjConst* oc, ObjState* st, const int* mcnt, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_sum_m, dim3(B), dim3(256), 0, s, oc, st, mcnt);
 }
 void launch_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow,
-                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_gram, dim3(n_slices, B, n_terms), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, alive, partials, n_slices, b_sdf, b_render, robust);
+                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s,
+                 const ObsWeightsDev* ow) {
+    if (!ow) {
+        hipLaunchKernelGGL(k_gram<false>, dim3(n_slices, B, n_terms), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, alive, partials, n_slices, b_sdf, b_render,
+                           robust, (const float*)nullptr, (const float*)nullptr);
+        return;
+    }
+    hipLaunchKernelGGL(k_gram<true>, dim3(n_slices, B, n_terms), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, alive, partials, n_slices, b_sdf, b_render,
+                       robust, ow->pt_w, (const float*)ow->jw);
+    hipLaunchKernelGGL(k_weight_sums, dim3(B), dim3(256), 0, s, oc, st, ow->pt_w, (const float*)ow->jw, alive, n_terms == 1 ? 1 : 0, ow->sums);
 }
 void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow, int term, float* rows,
                   int cap, hipStream_t s) {
@@ -2390,7 +2478,8 @@ void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, co
 }
 void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
                   float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
-                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior, const StepDev* step) {
+                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior, const StepDev* step, const ObsWeightsDev* ow) {
+    const double* wn = ow ? (grp ? ow->gsums : ow->sums) : nullptr;
     const StepDev sd = step ? *step : StepDev{};
     const StopRule rule = stop ? *stop : StopRule{0.0, 0.0, 1};
     const PriorDev pr = prior ? *prior : PriorDev{};
@@ -2403,16 +2492,17 @@ void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, doubl
             k = prior ? (stop ? k_solve<false, true, true, true> : k_solve<false, false, true, true>)
                       : (stop ? k_solve<false, true, false, true> : k_solve<false, false, false, true>);
         hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr, sd);
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr, sd, wn);
         return;
     }
-    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B);
+    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B,
+                       ow ? (const double*)ow->sums : nullptr, ow ? ow->gsums : nullptr);
     if (prior) launch_prior_terms(st, prm, pr, grp, 0, B, s);
     if (step) throw std::invalid_argument("step control is not built for multi-view batches");
     auto k = prior ? (stop ? k_solve<true, true, true, false> : k_solve<true, false, true, false>)
                    : (stop ? k_solve<true, true, false, false> : k_solve<true, false, false, false>);
     hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
-                       (const int*)gmk, rule, pr, sd);
+                       (const int*)gmk, rule, pr, sd, wn);
     launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
 }
 void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s) {
@@ -2422,20 +2512,23 @@ void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_posterior_park, dim3((B + 63) / 64), dim3(64), 0, s, st, park, B);
 }
 void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
-                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk, const PriorDev* prior) {
+                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk, const PriorDev* prior,
+                      const ObsWeightsDev* ow) {
     // the reductions launch_solve runs (no trace row), then the record
+    const double* wn = ow ? (grp ? ow->gsums : ow->sums) : nullptr;
     const PriorDev pr = prior ? *prior : PriorDev{};
     hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
     if (!grp) {
         auto k = prior ? k_posterior<false, true> : k_posterior<false, false>;
         hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride, pr);
+                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride, pr, wn);
         return;
     }
-    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, 0, (float*)nullptr, B);
+    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, 0, (float*)nullptr, B,
+                       ow ? (const double*)ow->sums : nullptr, ow ? ow->gsums : nullptr);
     auto k = prior ? k_posterior<true, true> : k_posterior<true, false>;
     hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park, grp,
-                       (const int*)gmk, rec, rec_stride, pr);
+                       (const int*)gmk, rec, rec_stride, pr, wn);
 }
 void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
     hipLaunchKernelGGL(k_group_broadcast, dim3(B), dim3(64), 0, s, grp, st, cbias, depths, n_depth);

@@ -206,6 +206,29 @@ class Batch(object):
         out.update(self._member_offsets(n_m))
         return out
 
+    # ---- per-observation weights (dsp_batch_observation_weights, include/dsp_gn.h): the input the report's answer is fed back through -------
+    def set_observation_weights(self, pt_w=None, ray_w=None):
+        """pt_w: one weight per surface point, ray_w: one per ray (foreground rays first), each a concatenated array in MEMBER order -- the
+        layout of report() -- or a list of per-member arrays.  None = all ones for that kind; both None = off, the initial state.  A
+        weight multiplies the observation's squared residual and the means divide by the weight sums; a ray of weight 0 is absent.  The
+        weights stay set for the following runs.  A pose-only batch ignores ray_w."""
+        lib, h = L.load(), self.engine._h
+        n_p, n_r, n_m = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(lib.dsp_batch_report_sizes(self._h, C.byref(n_p), C.byref(n_r), C.byref(n_m)), h, "dsp_batch_report_sizes")
+
+        def flat(w, n, what):
+            if w is None:
+                return None
+            if isinstance(w, (list, tuple)):
+                w = np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in w]) if len(w) else np.zeros(0, np.float32)
+            w = L.f32(np.asarray(w, np.float32).reshape(-1))
+            if w.size != n:
+                raise ValueError("set_observation_weights: %s has %d entries, the batch has %d" % (what, w.size, n))
+            return w
+        pw = flat(pt_w, n_p.value, "pt_w")
+        rw = None if self.pose_only else flat(ray_w, n_r.value, "ray_w")
+        L.check(lib.dsp_batch_observation_weights(self._h, L.ptr(pw), L.ptr(rw)), h, "dsp_batch_observation_weights")
+
     def _member_offsets(self, n_members):
         """pts_off / ray_off / depth_off per member as they were uploaded, and view_off (every object one member)."""
         if self.pose_only:
@@ -415,7 +438,7 @@ def _step_control_args(step_control):
     return dict(zip(("lambda0", "up", "down", "lambda_min", "lambda_max"), step_control))
 
 
-def _run_resident(b, convergence, posterior, prior, step_control=None, report=None):
+def _run_resident(b, convergence, posterior, prior, step_control=None, report=None, obs_weights=None):
     """The optional rules of the Engine's one-call forms on a resident batch: -> results() [+ (posterior(),)] [+ (report(),)] [+ (prior_residual(),)]."""
     if convergence is not None:
         b.set_convergence(*convergence)
@@ -427,6 +450,8 @@ def _run_resident(b, convergence, posterior, prior, step_control=None, report=No
         b.set_prior(*_prior_args(prior))
     if report:
         b.set_report(True)
+    if obs_weights is not None:
+        b.set_observation_weights(*obs_weights)
     b.run()
     return (b.results() + (() if posterior is None else (b.posterior(),)) + ((b.report(),) if report else ()) +
             (() if prior is None else (b.prior_residual(),)))
@@ -803,7 +828,7 @@ class Engine(object):
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
     def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, step_control=None, posterior=None,
-                          report=None, prior=None):
+                          obs_weights=None, report=None, prior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
         convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
         posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
@@ -813,7 +838,8 @@ class Engine(object):
         step_control: None (off), True (the defaults), a dict of Batch.set_step_control's keyword arguments or a (lambda0, up, down,
         lambda_min, lambda_max) tuple; the returned items are the same, `loss` is then the loss AT the returned state.
         report: None / False, or True -- Batch.set_report; the call then returns Batch.report() behind the posterior (in front of the prior's
-        residual, which stays last)."""
+        residual, which stays last).
+        obs_weights: None, or (pt_w, ray_w) -- Batch.set_observation_weights; the returned items are the same."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
             return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
@@ -821,7 +847,7 @@ class Engine(object):
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
-            return _run_resident(b, convergence, posterior, prior, step_control, report)
+            return _run_resident(b, convergence, posterior, prior, step_control, report, obs_weights)
         finally:
             b.close()
 
@@ -829,18 +855,19 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, report=None, prior=None):
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, obs_weights=None, report=None, prior=None):
         """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
         convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call.
-        posterior, report, prior: as reconstruct_batch (a resident batch too; further items, per object -- the report's rows per VIEW)."""
+        posterior, report, prior: as reconstruct_batch (a resident batch too; further items, per object -- the report's rows per VIEW).
+        obs_weights: as reconstruct_batch, per VIEW (a resident batch too)."""
         n = len(views)
         if n == 0:
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
             return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
-        if convergence is not None or posterior is not None or prior is not None or report:
+        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None:
             b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
             try:
-                return _run_resident(b, convergence, posterior, prior, None, report)
+                return _run_resident(b, convergence, posterior, prior, None, report, obs_weights)
             finally:
                 b.close()
         vo, t_ref, pts, rays, depth = _flatten_views(views)
@@ -856,19 +883,20 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, report=None, prior=None):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, obs_weights=None, report=None, prior=None):
         """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
         one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior()).
         report: as reconstruct_batch; Batch.report() follows the posterior (the alive bits are the inlier filter's mask).
-        prior: as reconstruct_batch, with (6, 6) Lambdas and t_obj_cam0 carrying the scale; Batch.prior_residual() is then the last item."""
+        prior: as reconstruct_batch, with (6, 6) Lambdas and t_obj_cam0 carrying the scale; Batch.prior_residual() is then the last item.
+        obs_weights: as reconstruct_batch (a resident batch too); the ray weights are ignored."""
         n = len(pts)
         if n == 0:
             extra = (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
             return np.zeros((0, 4, 4), np.float32) if not extra else (np.zeros((0, 4, 4), np.float32),) + extra
-        if convergence is not None or posterior is not None or prior is not None or report:
+        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None:
             b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
             try:
-                res = _run_resident(b, convergence, posterior, prior, None, report)
+                res = _run_resident(b, convergence, posterior, prior, None, report, obs_weights)
                 return res[0] if len(res) == 4 else (res[0],) + res[4:]
             finally:
                 b.close()

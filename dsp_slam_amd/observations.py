@@ -83,3 +83,17 @@ def silhouette_disagreement(report, n_fg=None):
         if bg.size:
             bg_hit[i] = float(np.mean(bg > 0.5))
     return dict(fg_miss=fg_miss, bg_hit=bg_hit)
+
+
+def reject(report, pt_sdf_max, ray_res_max):
+    """The report turned into per-observation weights (Batch.set_observation_weights): (pt_w, ray_w) of float32, concatenated in member
+    order like the report.  pt_w is 0 where |pt_sdf| > pt_sdf_max or the point is not alive (dropped by the pose-only inlier filter, or its
+    member was not evaluated), ray_w is 0 where |ray_residual| > ray_res_max; 1 elsewhere.  A ray whose row is NaN (its member had no
+    render term, or the ray was already absent) keeps 1: nothing is known against it."""
+    sdf = np.asarray(report["pt_sdf"])
+    alive = np.asarray(report["pt_alive"], bool)
+    res = np.asarray(report["ray_residual"])
+    with np.errstate(invalid="ignore"):
+        pt_w = np.where((np.abs(sdf) > float(pt_sdf_max)) | ~alive, 0.0, 1.0).astype(np.float32)
+        ray_w = np.where(np.abs(res) > float(ray_res_max), 0.0, 1.0).astype(np.float32)
+    return pt_w, ray_w

@@ -525,7 +525,33 @@ int dsp_batch_report_fetch(dsp_batch* b, float* pt_sdf, uint8_t* pt_flags, float
 int dsp_debug_report_ray(int32_t n_depth, const float* depths, const float* sdf /* NaN = not in the sphere */, float th, float depth_obs,
                          int is_fg, float* out4, int32_t* counts3);
 
-/* ---- testing: ONE door for the forms the library chooses between by itself -----------------------------------------------------------
+/* ---- per-observation weights (optional): the input the report's answer can be fed back through ---------------------------------------------
+ * pt_w: one float per surface point; ray_w: one float per ray (foreground rays first, as uploaded); both concatenated in MEMBER order, exactly
+ * as dsp_batch_report_fetch lays its rows out (dsp_batch_report_sizes gives the lengths).  Either may be NULL = all ones for that kind; both
+ * NULL = off (initial): the run launches the kernels of a batch that never had weights and returns the same bits.  A pose-only batch ignores
+ * ray_w.  The values are copied to the device (arrays from the handle's pool the first time: DSP_E_NOMEM leaves weights off and the batch
+ * usable) and stay set for every following run, a partial re-run after a prepass-guard trip included, until changed.
+ * The objective (priors and damping unchanged):
+ *   E = k2 sum_p w_p (rho_b2 r_p)^2 / sum_p w_p  +  k1 sum_k w_ray(k) (rho_b1 r_k)^2 / sum_k w_ray(k)
+ * p over the surface points (a pose-only batch: the points alive, raw residual), k over the KEPT render rows, each with the weight of its
+ * ray: H gets sum w J^T J, b gets -sum w J^T r~, and the divisors M / K (pose-only: the points alive) are replaced by the fp64 sums of the
+ * weights, taken in a fixed order; a multi-view object pools both sums over its views.  The device multiplies every row by the correctly
+ * rounded float32 square root of its weight.
+ * A RAY OF WEIGHT 0 IS ABSENT: not sampled -- nothing in V, m, K, the "< 10 in-sphere samples" rule or the decoder's work -- and its report
+ * rows are those of a member without a render term (NaN floats, zero counts).  A point of weight 0 is decoded and contributes a zero row.
+ * sum_p w_p == 0 ends the object DSP_OBJ_NAN (as M == 0 does); every ray at 0 is V == 0: DSP_OBJ_FEW_SAMPLES; a view whose weights are all
+ * 0 behaves as a view given no observations.  The integer counts of traces, posterior records and report members stay counts.
+ * With all weights 1 every result bit equals a run without weights.  Composes with the convergence rule, step control (the cost is the
+ * weighted loss), the prior, the posterior (MEAN divides by the weight sums; SUM applies k2 / k1 to the weighted Grams: the weights act as
+ * inverse-variance factors) and the report (pt_sdf and ray_* stay raw; sum_s / sum_r become the weighted sums, and the loss identity holds
+ * with the weight sums, which the caller forms from its weights, the alive bits and ray_counts[:, 2]), in both compute modes and every
+ * launch form.  DSP_E_ARG (previous setting kept): a negative or non-finite weight, a stale token.  The one-shot calls have no weights.
+ * (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+int dsp_batch_observation_weights(dsp_batch* b, const float* pt_w, const float* ray_w);
+/* Testing (host only, no device): dsp_batch_observation_weights' checks on n_points / n_rays values (NULL = all ones: nothing to check). */
+int dsp_debug_observation_weights_check(int64_t n_points, int64_t n_rays, const float* pt_w, const float* ray_w);
+
+/* ---- testing: ONE door for the forms the library chooses between by itself-----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */
 #define DSP_DBG_MASK_REUSE 1        /* render rows run the backward sweep only, from relu masks the forward launches exported (throughput form: a launch of their own) */

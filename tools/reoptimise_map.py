@@ -37,6 +37,11 @@ each result is printed: a large value says the new data contradicts the old esti
 --step-control L0 UP DOWN LMIN LMAX (off without the flag) switches Levenberg-Marquardt step control on (dsp_batch_step_control): a state is
 kept only if it lowers the loss, a rejected step is solved again with more damping, and the loss written is the loss AT the returned state.
 Conventional values: 0 10 0.1 1 inf.  The accepted / rejected counts are printed.  Not for maps with multi-view objects.
+
+--reject PT_SDF RAY_RES (off without the flag) runs every shard twice on the SAME resident batch: once with the observation report, then --
+with the surface points whose |sdf| exceeds PT_SDF and the rays whose |depth residual| exceeds RAY_RES at the first result given weight 0
+(dsp_slam_amd.observations.reject, dsp_batch_observation_weights) -- once more from the same start; nothing is uploaded again but the two
+weight arrays.  The second run's results are written; the rejected counts are printed.
 """
 import argparse
 import os
@@ -115,7 +120,7 @@ def prior_arrays(prior, objs, obs, idx):
 
 
 def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None,
-               step_control=None, report=False):
+               step_control=None, report=False, reject=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
@@ -129,8 +134,12 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     (accepted, rejected) counted over all observed objects and iterations.
     report: True switches the observation report on (Batch.set_report); stats["report"] then maps "<object id>/<key>" to that object's rows
     (dsp_slam_amd.observations.object_rows: per-point sdf and alive bits, per-ray depth / hit / residual / counts, per-view sums), as
-    numpy.savez takes them."""
+    numpy.savez takes them.
+    reject: None, or (pt_sdf_max, ray_res_max): every shard runs with the report, turns it into 0 / 1 observation weights
+    (observations.reject, Batch.set_observation_weights) and runs again on the same resident batch; everything returned is the second
+    run's, and stats["rejected"] holds (points, rays) given weight 0, counted over all observed objects."""
     from dsp_slam_amd import distributed as D
+    from dsp_slam_amd import observations as OBS
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
     for i in idx:
@@ -151,6 +160,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         raise ValueError("step control does not take multi-view objects")
     steps = [None] * len(shards)
     reports = [None] * len(shards)
+    rejected = [None] * len(shards)
     if multiview and compute != 0:
         raise ValueError("the low-precision compute mode does not take multi-view objects")
 
@@ -158,7 +168,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if (tol is not None or posterior is not None or pri is not None or step_control is not None or report) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None or pri is not None or step_control is not None or report or reject is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -174,9 +184,15 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                     bt.set_prior(pri[0][a:b], pri[1][a:b], pri[2][a:b])
                 if step_control is not None:
                     bt.set_step_control(*step_control)
-                if report:
+                if report or reject is not None:
                     bt.set_report(True)
                 bt.run()
+                if reject is not None:      # report -> weights -> the same batch once more
+                    pt_w, ray_w = OBS.reject(bt.report(), reject[0], reject[1])
+                    rejected[r] = (int((pt_w == 0).sum()), int((ray_w == 0).sum()))
+                    bt.set_observation_weights(pt_w, ray_w)
+                    bt.set_report(bool(report))
+                    bt.run()
                 if report:
                     reports[r] = bt.report()
                 if step_control is not None:
@@ -250,7 +266,8 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                     rows["%d/%s" % (objs[idx[k]]["id"], key)] = val
                 k += 1
     step_decisions = None if step_control is None else tuple(int(sum(x[k] for x in steps if x is not None)) for k in (0, 1))
-    return out, dict(step_decisions=step_decisions, prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
+    n_rejected = None if reject is None else tuple(int(sum(x[k] for x in rejected if x is not None)) for k in (0, 1))
+    return out, dict(rejected=n_rejected, step_decisions=step_decisions, prior_chi2=prior_chi2, n_objects=len(objs), n_observed=len(idx), n_good=n_good, seconds=dt, shards=[tuple(s) for s in shards], packed=packed,
                      iterations_used=iters, posterior=records, report=rows)
 
 
@@ -275,6 +292,8 @@ def main():
     ap.add_argument("--report", default=None, metavar="FILE.npz",
                     help="write every observed object's observation report at its result, keyed '<object id>/<field>': per-point sdf and alive bits, per-ray "
                          "depth / hit / residual / counts, per-view sums (dsp_slam_amd.observations reads them)")
+    ap.add_argument("--reject", type=float, nargs=2, metavar=("PT_SDF", "RAY_RES"), default=None,
+                    help="run twice on the same resident batch: observations whose |sdf| / |depth residual| at the first result exceed these bounds get weight 0 in the second")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -290,13 +309,15 @@ def main():
                          tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum",
                          posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)),
                          step_control=None if args.step_control is None else tuple(args.step_control),
-                         report=args.report is not None)
+                         report=args.report is not None, reject=None if args.reject is None else tuple(args.reject))
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (
         st["n_good"], st["n_objects"], st["n_observed"], n_dev, st["seconds"], st["n_observed"] / max(st["seconds"], 1e-9), dst))
     if st["iterations_used"] is not None:
         print("iterations used: %s" % iterations_histogram(st["iterations_used"]))
+    if st["rejected"] is not None:
+        print("rejected after the first run: %d surface points, %d rays" % st["rejected"])
     if st["step_decisions"] is not None:
         print("step control: %d states accepted, %d rejected" % st["step_decisions"])
     if st["prior_chi2"] is not None:

@@ -184,6 +184,10 @@ constexpr int DSP_STATUS_SKIP = 3;   // internal: not part of this (partial re-)
 // "not GOOD" to every kernel -- no tiles, rows, guard samples, no write to the state -- but k_finalize writes its row and reports DSP_OBJ_GOOD
 constexpr int DSP_STATUS_DONE = 4;
 constexpr int MAX_DEPTH_SAMPLES = 64;
+// the run summary, ONE device block of 32-bit words: [8 fp64 work counters | 4 audit words | B x {margin, trips, max error} | B words: updates applied]
+constexpr int SUM_COUNTERS = 0, SUM_AUDIT = 16, SUM_GUARD = 20, SUM_GUARD_WORDS = 3;
+constexpr int SUM_HEAD_WORDS = SUM_GUARD;       // what a run zeroes at its start: the counters and the audit words
+constexpr size_t sum_iters(int B) { return SUM_GUARD + (size_t)B * SUM_GUARD_WORDS; }
 constexpr int TRACE_STRIDE = 5344;   // 71*71 H | 71 b | 71 dx | 16 t_oc | 64 code | V m K | vsum lo,hi | ksum lo,hi | pad | 64 depths
 
 struct ObjConst {           // static layout of one object inside the batch arrays
@@ -329,6 +333,82 @@ struct ObsWeightsDev {
     double* gsums = nullptr;        // multi-view batches, 2 per member, written at the leaders: the group's pooled sums (k_group_reduce)
 };
 
+// Observation report (dsp_batch_report): the device arrays of one batch, in the order of the inputs -- points by pts_off, rays by ray_off,
+// 8 doubles per member.
+struct ReportDev {
+    float* pt_sdf = nullptr;
+    unsigned char* pt_flags = nullptr;
+    float* ray_depth = nullptr;
+    float* ray_hit = nullptr;
+    float* ray_residual = nullptr;
+    int* ray_counts = nullptr;      // 3 per ray: in-sphere, band, kept
+    double* member = nullptr;       // 8 per member: M, V, m, K, sum_s, sum_r, status, 0
+};
+
+// One run's view of a batch for the Gauss-Newton launchers below: the stream, the sizes, the settings and every device array they address.
+// The host fills it ONCE per run (dsp_gn.hip: fill_view, behind plan_run and size_run_buffers, so every pointer holds for the whole run) and
+// applies there the rules whose answer is fixed for a run; a launcher's body is the one place that says which arrays its kernel reads.
+struct GnView {
+    hipStream_t s = nullptr;
+    int B = 0, D = 0, maxR = 0, maxM = 0, n_slices = 1;
+    GnParamsDev prm{};
+    const ObjConst* oc = nullptr;
+    ObjState* st = nullptr;
+    const float *pts = nullptr, *rays = nullptr, *depth = nullptr;      // the inputs; depth: the observed foreground depths
+    // start of a run (k_init_state): t_start holds object->camera estimates (the reference's argument) or -- init_flags bit 1 -- camera->object
+    // matrices taken as they are (bit 0: pose-only); codes_start optional; depths_start: optional B x 64 override of the first depth samples
+    const float *t_start = nullptr, *codes_start = nullptr, *scale = nullptr, *depths_start = nullptr;
+    int init_flags = 0;
+    const unsigned char* run_mask = nullptr;    // optional, B bytes: objects with a zero byte are left out of the run (DSP_STATUS_SKIP, state and result row untouched)
+    unsigned* summary = nullptr;                // the run summary (SUM_*); k_init_state zeroes its head
+    // per-ray bookkeeping and the sample list
+    unsigned long long* raymask = nullptr;
+    int *raycnt = nullptr, *rayoff = nullptr, *kcnt = nullptr, *koff = nullptr, *mcnt = nullptr, *pcnt = nullptr, *poff = nullptr, *plist = nullptr;
+    unsigned char* ray_alive = nullptr;
+    float *ray_res = nullptr, *ssdf = nullptr, *sdeds = nullptr;
+    const float* saudit = nullptr;              // prepass audit: the fp32 value of every in-sphere sample
+    float4* spts = nullptr;
+    // jacobian rows: surface points, then kept render rows
+    float4* jpts = nullptr;
+    float2* jaux = nullptr;
+    float* jgrad = nullptr;
+    int *srow = nullptr, *jrow = nullptr;       // speculative band rows, null unless the plan is speculative: jgrad row of a sample / of kept render row i
+    unsigned char* alive = nullptr;             // inlier flags of the surface points; null unless the batch is pose-only
+    int4 *tiles_f = nullptr, *tiles_j = nullptr;    // tile lists of the decoder launches ...
+    int* n_tiles = nullptr;                         // ... and their counts, slot LIST_*
+    float* partials = nullptr;
+    double* gsum = nullptr;
+    float* trace = nullptr;                     // optional: TRACE_STRIDE floats per iteration and member
+    const float *codew = nullptr, *b0 = nullptr, *blat = nullptr;   // the decoder's code columns: k_solve writes the next iteration's code bias ...
+    float* cbias = nullptr;                                         // ... here
+    const float* depth_sched = nullptr;         // optional [iteration][member][64]: row e + 1 overrides the depth samples k_solve derives in iteration e
+    int sched_iters = 0;
+    // multi-view groups (both set, or both null = every member is an object of its own): the members' Gram sums are pooled at the leader
+    // (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
+    const GroupEnt* grp = nullptr;
+    int* gmk = nullptr;
+    // optional features, all null = off: the launches and kernel instantiations are those of a batch without the feature
+    ObsWeightsDev obs;              // on: the weighted k_gram with k_weight_sums behind it, and the means divide by the weight sums
+    PriorDev prior;                 // on: k_prior_terms in front of k_solve / k_posterior, Lambda and g include the prior's block
+    StopRule stop{0.0, 0.0, 1};     // the convergence rule; off = a pose tolerance of 0, which can stop nothing
+    StepDev step;                   // Levenberg-Marquardt step control (StepDev::last is set per launch)
+    ReportDev report;
+    bool weighted() const { return obs.sums != nullptr; }
+    bool has_prior() const { return prior.extra != nullptr; }
+    bool stops() const { return stop.pose_tol > 0.0; }
+    bool step_control() const { return step.sys != nullptr; }
+    // the pass at the returned state: every member's status word is parked in park[] in front of it (frozen objects, DSP_STATUS_DONE, take part
+    // as good ones).  Posterior (post_level 0 = off): one record of post_stride doubles per OBJECT (POSTERIOR_REC_L1, or _L2 with Lambda, g and
+    // the state); post_weights: DSP_POSTERIOR_MEAN / _SUM
+    int post_level = 0, post_weights = 0, post_stride = 0;
+    int* park = nullptr;
+    double* post_rec = nullptr;
+    // results (k_finalize): one row per OBJECT, a group's written by its leader
+    float* packed = nullptr;
+    int guard_on = 0;               // the prepass guard is on: what it saw goes to the summary's guard words
+};
+enum { LIST_FWD = 0, LIST_JAC = 1, LIST_AUDIT = 3 };     // the lists k_build_tiles fills: tiles_f; tiles_j; tiles_j again (free while the audit runs)
+
 // kernels_mlp / kernels_gn launchers
 size_t mlp_lds_bytes(int mode);
 void launch_code_bias(const float* codew, const float* b0, const float* blat, const float* codes, int code_stride, float* out, int n_obj, hipStream_t s);
@@ -342,42 +422,29 @@ hipError_t mlp_lp_prepare_device();
 hipError_t launch_mlp_lp(bool bf16, const LpArgs& args, int n_blocks, hipStream_t stream, int tile_pts = LP_TILE_PTS);   // 128- or 64-point tiles, forward only
 hipError_t mlp_lpj_prepare_device();
 hipError_t launch_mlp_lpj(int which, bool bf16, const LpjArgs& args, int n_blocks, hipStream_t stream);   // 128-point tiles; which: 0 forward + mask export, 1 backward from the masks
-// run_mask (optional, B bytes): objects with a zero byte are left out of the run (status DSP_STATUS_SKIP, state and result row untouched);
-// summary: the run's counter words, zeroed here (summary_words of them)
-void launch_init_state(ObjState* st, const float* t, const float* codes, const float* scale, const float* depths /*optional B x 64*/, int B, int D, int pose_only,
-                       const LpDeltaTab& lp, const unsigned char* run_mask, unsigned* summary, int summary_words, hipStream_t s);
-void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s,
-                         const float* ray_w = nullptr);   // ray_w (observation weights, optional): a ray of weight 0 gets an empty mask
-void launch_scan_rays(const ObjConst* oc, ObjState* st, const int* cnt, int* off, int which, int B, hipStream_t s);
-void launch_sample_write(const ObjConst* oc, const ObjState* st, const float* rays, const unsigned long long* m, const int* off, float4* spts,
-                         float* ssdf, unsigned char* alive, int D, int maxR, int B, hipStream_t s);
-void launch_surface(const ObjConst* oc, const ObjState* st, const float* pts, float4* jpts, float2* jaux, int maxM, int B, hipStream_t s);
-void launch_build_tiles(const ObjConst* oc, ObjState* st, int B, int mode, int4* tiles, int* n_tiles, double* counters, int add_v, int tile_pts,
-                        int cnt_slot, hipStream_t s, int apply_few = 0);   // mode 3 = mode 1 with the band samples (P) in place of the kept render rows (K)   // cnt_slot: counter the point count of a mode 0 / 2 list is added to
-// th = cut_off; the widened band of object b is |sdf_lp| < th + st[b].lp_delta.  guard_salt: samples OUTSIDE the band whose id hash
-// (xor salt) selects them (1/8 of the ring just beyond the band, 1/512 farther out) are listed too, so that the fp32 kernel re-decodes them
-// and prepass_guard compares (0 = no guard samples)
 void launch_tail_tiles(const int4* tiles, int* n_tiles, int4* tiles16, int* n_tiles16, int n_cu, hipStream_t s);   // see k_tail_tiles
-void launch_band_select(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th,
-                        unsigned guard_salt, int* pcnt, int* poff, int* plist, int maxR, int B, hipStream_t s);
-// wave-per-ray forms (latency path; one wave per ray, 16 rays per workgroup, whole chip) of front = sample_count + scan + sample_write +
-// surface, band = count + scan + write, render tail = scan + sum_m + render_write (behind k_render_scan): list segments from running counters
-// (ObjState::V / ::P) instead of scans; kept rows stay in ray-major order.  See gn_kernels.hip.
-void launch_front_wave(const ObjConst* oc, ObjState* st, const float* rays, const float* pts, unsigned long long* raymask, int* raycnt, int* rayoff,
-                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s,
-                       const float* ray_w = nullptr);
-void launch_band_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th, unsigned guard_salt,
-                      int* plist, const float4* spts, float4* jpts, int* srow, int maxR, int B, hipStream_t s);   // jpts / srow: speculative band rows (or null)
-void launch_render_tail_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float4* spts, const float* sdeds,
-                             const float* ray_res, const int* kcnt, const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow, int maxR, int B,
-                             hipStream_t s, const float* ray_w = nullptr, float* jw = nullptr);   // ray_w / jw (both or neither): every kept row's weight
-void launch_prepass_audit(const ObjConst* oc, const ObjState* st, const float* ssdf, const float* saudit, float th, unsigned* out,
-                          int B, hipStream_t s);
-void launch_render_scan(const ObjConst* oc, ObjState* st, const unsigned long long* m, const int* off, const float* ssdf, const float* depth,
-                        float* sdeds, float* ray_res, int* kcnt, int* mcnt, int D, float th, int maxR, int B, hipStream_t s);
-void launch_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff, const float4* spts,
-                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s,
-                         const float* ray_w = nullptr, float* jw = nullptr);
+
+// ---- Gauss-Newton launchers: the view, plus what varies from call to call ----
+void launch_init_state(const GnView& v);
+// throughput forms of the per-ray bookkeeping (one thread block per 256 rays + a scan launch per list): front = sample_count + scan +
+// sample_write (with observation weights a ray of weight 0 gets an empty mask), pass_list = pass_select + scan + pass_write, band_select =
+// count + scan + write, render_tail = scan + sum_m + render_write (behind k_render_scan; every kept row's weight goes to ObsWeightsDev::jw)
+void launch_front(const GnView& v);
+void launch_surface(const GnView& v);
+// mode 3 = mode 1 with the band samples (P) in place of the kept render rows (K); cnt_slot: counter the point count of a mode 0 / 2 list is added to
+void launch_build_tiles(const GnView& v, int mode, int list, int add_v, int tile_pts, int cnt_slot, int apply_few);
+// the band of object b is |sdf_lp| < cut_off + st[b].lp_delta.  guard_salt: samples OUTSIDE the band whose id hash (xor salt) selects them (1/8 of
+// the ring just beyond the band, 1/512 farther out) are listed too, so that the fp32 kernel re-decodes them and prepass_guard compares (0 = no
+// guard samples)
+void launch_band_select(const GnView& v, unsigned guard_salt);
+// wave-per-ray forms (latency path; one wave per ray, 16 rays per workgroup, whole chip) of front (+ surface), band and render tail: list
+// segments from running counters (ObjState::V / ::P) instead of scans; kept rows stay in ray-major order.  See gn_kernels.hip.
+void launch_front_wave(const GnView& v);
+void launch_band_wave(const GnView& v, unsigned guard_salt);
+void launch_render_tail_wave(const GnView& v);
+void launch_prepass_audit(const GnView& v);
+void launch_render_scan(const GnView& v);
+void launch_render_tail(const GnView& v);
 // one front-to-back forward pass: fixed depth-index range [j0, j1) (hint == nullptr), or per-ray adaptive ranges where
 // j0 = margin added to the hint in pass 0 and j1 = step of the middle passes
 struct PassSpec {
@@ -385,60 +452,32 @@ struct PassSpec {
     unsigned char* hint;   // per ray: depth index of the first solid sample in the previous GN iteration
     unsigned char* plo;    // per ray: end of the range decoded so far in this iteration
 };
-void launch_pass_select(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const unsigned char* alive,
-                        int* pcnt, const PassSpec& ps, int maxR, int B, hipStream_t s);
-void launch_pass_write(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff, const unsigned char* alive,
-                       const int* poff, int* plist, const PassSpec& ps, int maxR, int B, hipStream_t s);
-void launch_pass_update(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff, unsigned char* alive,
-                        const float* ssdf, float th, int use_lp_delta, const PassSpec& ps, int maxR, int B, hipStream_t s);   // use_lp_delta: a ray stops at sdf <= -(th + st[b].lp_delta)
-void launch_sum_m(const ObjConst* oc, ObjState* st, const int* mcnt, int B, hipStream_t s);
-void launch_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow,
-                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s,
-                 const ObsWeightsDev* ow = nullptr);   // ow: the weighted instantiation, and k_weight_sums behind it (nullptr: the kernel without weights, alone)
-void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow, int term, float* rows,
-                  int cap, hipStream_t s);   // jrow (optional): render row i takes its gradient from jgrad row jrow[i]
-// grp / gmk (both or neither; nullptr = every member is an object of its own): multi-view groups -- the members' Gram sums are pooled at the
-// leader (k_group_reduce), only leaders solve, and the new pose and code go back to the members (k_group_broadcast); gmk = 2 ints per member
-void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
-                  float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B,
-                  hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr, const StopRule* stop = nullptr, const PriorDev* prior = nullptr,
-                  const StepDev* step = nullptr, const ObsWeightsDev* ow = nullptr);    // ow: the means divide by the weight sums   // step: Levenberg-Marquardt step control, nullptr = off (the kernel without it)   // stop: the convergence rule, nullptr = off (the kernel without it)   // cbias: next iteration's code bias; depths_next: optional B x 64 override of the next iteration's depth samples
+void launch_pass_list(const GnView& v, const PassSpec& ps);
+void launch_pass_update(const GnView& v, int use_lp_delta, const PassSpec& ps);   // use_lp_delta: a ray stops at sdf <= -(cut_off + st[b].lp_delta)
+void launch_gram(const GnView& v);
+void launch_jrows(const GnView& v, int term, float* rows, int cap);
+// one update: the reductions, the prior's terms, k_solve and -- groups -- the broadcast; last: the run's last iteration (StepDev::last)
+void launch_solve(const GnView& v, int iter, int last);
 // the members of every group take the leader's state: t_oc = T_oc * t_ref, the derived state (depths: optional B x 64 override), code, margin and
-// -- cbias given -- the code-bias row; a failed leader's status goes to its members.  Also run once behind k_init_state (cbias = nullptr).
-void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s);
-void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s);
-// posterior pass (dsp_batch_posterior).  launch_posterior_park: every member's status word into park[], frozen objects (DSP_STATUS_DONE) take
-// part as good ones.  launch_posterior: launch_solve's reductions (no trace), then k_posterior: one record of rec_stride doubles per OBJECT
-// (POSTERIOR_REC_L1, or _L2 with Lambda, g and the state), and the parked status words go back.  weights: DSP_POSTERIOR_MEAN / _SUM.
+// -- cbias given -- the code-bias row; a failed leader's status goes to its members.  start: once behind k_init_state (no code-bias row,
+// depths_start); otherwise the leader's LAST state in front of the pass at the returned state
+void launch_group_broadcast(const GnView& v, bool start);
+void launch_inlier_filter(const GnView& v);
+// posterior pass (dsp_batch_posterior).  launch_posterior: launch_solve's reductions (no trace), then k_posterior, and the parked status words go back.
 constexpr int POSTERIOR_REC_L1 = 168;
 constexpr int POSTERIOR_REC_L2 = POSTERIOR_REC_L1 + 71 * 71 + 71 + (16 + CODE_LEN + MAX_DEPTH_SAMPLES) / 2;
-void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s);
-void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
-                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp = nullptr, int* gmk = nullptr,
-                      const PriorDev* prior = nullptr, const ObsWeightsDev* ow = nullptr);      // prior: Lambda and g include the prior's block (launch_prior_terms goes first)
-// observation report (dsp_batch_report): the device arrays of one batch, in the order of the inputs -- points by pts_off, rays by ray_off,
-// 8 doubles per member.  launch_report runs k_report_rays / k_report_points / k_report_members behind the front of the pass at the
-// returned state; park (optional): k_report_members puts the parked status words back (the posterior is off: nobody else will).
+void launch_posterior_park(const GnView& v);
+void launch_posterior(const GnView& v);
+// launch_report runs k_report_rays / k_report_points / k_report_members behind the front of the pass at the returned state; with observation
+// weights sum_s / sum_r are the weighted sums and a ray of weight 0 reads as absent.
 // report_ray_host: report_math::ray compiled for the host in the translation unit that has contraction off (dsp_debug_report_ray).
-struct ReportDev {
-    float* pt_sdf = nullptr;
-    unsigned char* pt_flags = nullptr;
-    float* ray_depth = nullptr;
-    float* ray_hit = nullptr;
-    float* ray_residual = nullptr;
-    int* ray_counts = nullptr;      // 3 per ray: in-sphere, band, kept
-    double* member = nullptr;       // 8 per member: M, V, m, K, sum_s, sum_r, status, 0
-};
-void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
-                   const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
-                   int maxM, int B, hipStream_t s, const ObsWeightsDev* ow = nullptr);   // ow: sum_s / sum_r are the weighted sums; a ray of weight 0 reads as absent
+void launch_report(const GnView& v);
 void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3);
 // the prior's terms at the current state (launch_solve launches it itself, in front of k_solve); final_pass 1: e and chi2 at the returned
 // state instead; 2 (launch_solve with step control): the terms, and chi2 at the current state in the record's chi2 slot
-void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s);
+void launch_prior_terms(const GnView& v, int final_pass);
 constexpr int DSP_RESULT_WIDTH_DEV = 82;   // == DSP_RESULT_WIDTH (dsp_gn.h): t_cam_obj 16 | code 64 | loss | status
-void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out /*optional B x 3*/, hipStream_t s,
-                     const GroupEnt* grp = nullptr, unsigned* iters_out = nullptr /*optional B: ObjState::n_iter*/);   // grp: one row per OBJECT, written by the group's leader
+void launch_finalize(const GnView& v);
 
 hipError_t launch_debug_lie(int kind, const float* x_dev, float* out_dev, int n_depth, hipStream_t s);   // testing: exp_sim3 / exp_se3 / rotation prior as k_solve evaluates them
 

@@ -2365,181 +2365,155 @@ __global__ __launch_bounds__(256) void k_code_bias(const float* codew, const flo
 void launch_code_bias(const float* codew, const float* b0, const float* blat, const float* codes, int code_stride, float* out, int n_obj, hipStream_t s) {
     hipLaunchKernelGGL(k_code_bias, dim3(n_obj), dim3(256), 0, s, codew, b0, blat, codes, code_stride, out);
 }
-void launch_init_state(ObjState* st, const float* t, const float* codes, const float* scale, const float* depths, int B, int D, int pose_only,
-                       const LpDeltaTab& lp, const unsigned char* run_mask, unsigned* summary, int summary_words, hipStream_t s) {
-    hipLaunchKernelGGL(k_init_state, dim3((B + 63) / 64), dim3(64), 0, s, st, t, codes, scale, depths, B, D, pose_only, lp, run_mask, summary, summary_words);
-}
-void launch_sample_count(const ObjConst* oc, ObjState* st, const float* rays, unsigned long long* m, int* c, int D, int maxR, int B, hipStream_t s,
-                         const float* ray_w) {
-    hipLaunchKernelGGL(k_sample_count, GRID2(maxR, B), dim3(256), 0, s, oc, st, rays, m, c, D, ray_w);
-}
-void launch_scan_rays(const ObjConst* oc, ObjState* st, const int* cnt, int* off, int which, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_scan_rays, dim3(B), dim3(256), 0, s, oc, st, cnt, off, which);
-}
-void launch_sample_write(const ObjConst* oc, const ObjState* st, const float* rays, const unsigned long long* m, const int* off, float4* spts,
-                         float* ssdf, unsigned char* alive, int D, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_sample_write, dim3((unsigned)std::max(1, (maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, st, rays, m, off, spts, ssdf, alive, D);
-}
-void launch_pass_select(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const unsigned char* alive,
-                        int* pcnt, const PassSpec& ps, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_pass_select, GRID2(maxR, B), dim3(256), 0, s, oc, st, raymask, rayoff, alive, pcnt, ps.j0, ps.j1, ps.n_depth, ps.pass,
-                       ps.last, ps.hint, ps.plo);
-}
-void launch_pass_write(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff, const unsigned char* alive,
-                       const int* poff, int* plist, const PassSpec& ps, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_pass_write, GRID2(maxR, B), dim3(256), 0, s, oc, st, raymask, rayoff, alive, poff, plist, ps.j0, ps.j1, ps.n_depth,
-                       ps.pass, ps.last, ps.hint, ps.plo);
-}
-void launch_pass_update(const ObjConst* oc, const ObjState* st, const unsigned long long* raymask, const int* rayoff, unsigned char* alive,
-                        const float* ssdf, float th, int use_lp_delta, const PassSpec& ps, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_pass_update, GRID2(maxR, B), dim3(256), 0, s, oc, st, raymask, rayoff, alive, ssdf, th, use_lp_delta, ps.j0, ps.j1, ps.n_depth,
-                       ps.pass, ps.last, ps.hint, ps.plo);
-}
-void launch_band_select(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th,
-                        unsigned guard_salt, int* pcnt, int* poff, int* plist, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_band_count, GRID2(maxR, B), dim3(256), 0, s, oc, st, raymask, rayoff, ssdf, th, guard_salt, pcnt);
-    hipLaunchKernelGGL(k_scan_rays, dim3(B), dim3(256), 0, s, oc, st, pcnt, poff, 2);
-    hipLaunchKernelGGL(k_band_write, GRID2(maxR, B), dim3(256), 0, s, oc, st, raymask, rayoff, ssdf, th, guard_salt, poff, plist);
-}
-void launch_prepass_audit(const ObjConst* oc, const ObjState* st, const float* ssdf, const float* saudit, float th, unsigned* out,
-                          int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_prepass_audit, dim3(64, B), dim3(256), 0, s, oc, st, ssdf, saudit, th, out);
-}
-void launch_front_wave(const ObjConst* oc, ObjState* st, const float* rays, const float* pts, unsigned long long* raymask, int* raycnt, int* rayoff,
-                       float4* spts, float* ssdf, unsigned char* alive, float4* jpts, float2* jaux, int D, int maxR, int maxM, int B, hipStream_t s,
-                       const float* ray_w) {
-    const int nrb = std::max(1, (maxR + WAVE_RAYS - 1) / WAVE_RAYS), nsb = (maxM + WAVE_THREADS - 1) / WAVE_THREADS;
-    hipLaunchKernelGGL(k_front_wave, dim3((unsigned)(nrb + nsb), (unsigned)B), dim3(WAVE_THREADS), 0, s, oc, st, rays, pts, raymask, raycnt, rayoff, spts, ssdf, alive,
-                       jpts, jaux, D, nrb, ray_w);
-}
-void launch_band_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float* ssdf, float th, unsigned guard_salt,
-                      int* plist, const float4* spts, float4* jpts, int* srow, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_band_wave, dim3((unsigned)std::max(1, (maxR + WAVE_RAYS - 1) / WAVE_RAYS), (unsigned)B), dim3(WAVE_THREADS), 0, s, oc, st, raymask, rayoff,
-                       ssdf, th, guard_salt, plist, spts, jpts, srow);
-}
-void launch_render_tail_wave(const ObjConst* oc, ObjState* st, const unsigned long long* raymask, const int* rayoff, const float4* spts, const float* sdeds,
-                             const float* ray_res, const int* kcnt, const int* mcnt, float4* jpts, float2* jaux, const int* srow, int* jrow, int maxR, int B,
-                             hipStream_t s, const float* ray_w, float* jw) {
-    hipLaunchKernelGGL(k_render_tail_wave, dim3((unsigned)std::max(1, (maxR + TAIL_RAYS - 1) / TAIL_RAYS), (unsigned)B), dim3(WAVE_THREADS), 0, s, oc, st, raymask,
-                       rayoff, spts, sdeds, ray_res, kcnt, mcnt, jpts, jaux, srow, jrow, ray_w, jw);
-}
-void launch_surface(const ObjConst* oc, const ObjState* st, const float* pts, float4* jpts, float2* jaux, int maxM, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_surface, GRID2(maxM, B), dim3(256), 0, s, oc, st, pts, jpts, jaux);
-}
-void launch_build_tiles(const ObjConst* oc, ObjState* st, int B, int mode, int4* tiles, int* n_tiles, double* counters, int add_v, int tile_pts,
-                        int cnt_slot, hipStream_t s, int apply_few) {
-    hipLaunchKernelGGL(k_build_tiles, dim3(1), dim3(256), 0, s, oc, st, B, mode, tiles, n_tiles, counters, add_v, tile_pts, cnt_slot, apply_few);
-}
 void launch_tail_tiles(const int4* tiles, int* n_tiles, int4* tiles16, int* n_tiles16, int n_cu, hipStream_t s) {
     hipLaunchKernelGGL(k_tail_tiles, dim3(1), dim3(256), 0, s, tiles, n_tiles, tiles16, n_tiles16, n_cu);
-}
-void launch_render_scan(const ObjConst* oc, ObjState* st, const unsigned long long* m, const int* off, const float* ssdf, const float* depth,
-                        float* sdeds, float* ray_res, int* kcnt, int* mcnt, int D, float th, int maxR, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_render_scan, dim3((unsigned)std::max(1, (maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, st, m, off, ssdf, depth, sdeds, ray_res,
-                       kcnt, mcnt, D, th);     // one wave per ray
-}
-void launch_report(const ObjConst* oc, ObjState* st, const ReportDev& rp, const unsigned long long* raymask, const int* rayoff, const float* ssdf,
-                   const float* depth_fg, const float2* jaux, const float* jgrad, const unsigned char* alive, const GnParamsDev& prm, const int* park, int maxR,
-                   int maxM, int B, hipStream_t s, const ObsWeightsDev* ow) {
-    if (!prm.pose_only && maxR > 0)
-        hipLaunchKernelGGL(k_report_rays, dim3((unsigned)((maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, (const ObjState*)st, raymask, rayoff, ssdf, depth_fg,
-                           prm.n_depth, prm.cut_off, rp.ray_depth, rp.ray_hit, rp.ray_residual, rp.ray_counts, ow ? ow->ray_w : nullptr);     // one wave per ray
-    if (maxM > 0)
-        hipLaunchKernelGGL(k_report_points, GRID2(maxM, B), dim3(256), 0, s, oc, (const ObjState*)st, jgrad, alive, rp.pt_sdf, rp.pt_flags);
-    hipLaunchKernelGGL(k_report_members, dim3(B), dim3(256), 0, s, oc, st, jaux, jgrad, alive, prm.b2, prm.b1, prm.pose_only ? 0 : 1, prm.pose_only, park,
-                       rp.member, ow ? ow->pt_w : nullptr, (ow && !prm.pose_only) ? (const float*)ow->jw : nullptr);
 }
 void report_ray_host(int n_depth, const float* depths, const float* sdf, float th, float depth_obs, int is_fg, float* out4, int* counts3) {
     report_math::ray(n_depth, depths, sdf, th, depth_obs, is_fg, out4, counts3);
 }
-void launch_render_write(const ObjConst* oc, const ObjState* st, const int* raycnt, const int* rayoff, const int* koff, const float4* spts,
-                         const float* sdeds, const float* ray_res, float4* jpts, float2* jaux, int maxR, int B, hipStream_t s, const float* ray_w, float* jw) {
-    hipLaunchKernelGGL(k_render_write, dim3((unsigned)std::max(1, (maxR + 3) / 4), (unsigned)B), dim3(256), 0, s, oc, st, raycnt, rayoff, koff, spts, sdeds, ray_res,
-                       jpts, jaux, ray_w, jw);     // one wave per ray
+
+// ---- Gauss-Newton launchers (GnView, dsp_internal.h): each body says which of the batch's arrays its kernel reads ----
+// (The code object lists template kernels in the order these bodies first name them: tools/compare_device_code.py sees a reordering as a change.)
+#define GRID_RAYS(v, per_block) dim3((unsigned)std::max(1, ((v).maxR + (per_block) - 1) / (per_block)), (unsigned)(v).B)
+#define GRID_OBJ(v) dim3((unsigned)(v).B)
+#define GRID_OBJ64(v) dim3((unsigned)(((v).B + 63) / 64))
+#define GRID_SYS(v, terms) dim3((72 * 72 + 255) / 256, (v).B, (terms))
+
+void launch_init_state(const GnView& v) {
+    hipLaunchKernelGGL(k_init_state, GRID_OBJ64(v), dim3(64), 0, v.s, v.st, v.t_start, v.codes_start, v.scale, v.depths_start, v.B, v.D, v.init_flags, v.prm.lp,
+                       v.run_mask, v.summary, SUM_HEAD_WORDS);
 }
-void launch_sum_m(const ObjConst* oc, ObjState* st, const int* mcnt, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_sum_m, dim3(B), dim3(256), 0, s, oc, st, mcnt);
+static void scan_rays(const GnView& v, int which) {      // which: 0 raycnt -> rayoff, 1 kcnt -> koff, 2 pcnt -> poff
+    const int* cnt = which == 0 ? v.raycnt : which == 1 ? v.kcnt : v.pcnt;
+    int* off = which == 0 ? v.rayoff : which == 1 ? v.koff : v.poff;
+    hipLaunchKernelGGL(k_scan_rays, GRID_OBJ(v), dim3(256), 0, v.s, v.oc, v.st, cnt, off, which);
 }
-void launch_gram(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow,
-                 const unsigned char* alive, float* partials, int n_slices, float b_sdf, float b_render, int robust, int n_terms, int B, hipStream_t s,
-                 const ObsWeightsDev* ow) {
-    if (!ow) {
-        hipLaunchKernelGGL(k_gram<false>, dim3(n_slices, B, n_terms), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, alive, partials, n_slices, b_sdf, b_render,
-                           robust, (const float*)nullptr, (const float*)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL(k_gram<true>, dim3(n_slices, B, n_terms), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, alive, partials, n_slices, b_sdf, b_render,
-                       robust, ow->pt_w, (const float*)ow->jw);
-    hipLaunchKernelGGL(k_weight_sums, dim3(B), dim3(256), 0, s, oc, st, ow->pt_w, (const float*)ow->jw, alive, n_terms == 1 ? 1 : 0, ow->sums);
+void launch_front(const GnView& v) {
+    hipLaunchKernelGGL(k_sample_count, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.rays, v.raymask, v.raycnt, v.D, v.obs.ray_w);
+    scan_rays(v, 0);
+    hipLaunchKernelGGL(k_sample_write, GRID_RAYS(v, 4), dim3(256), 0, v.s, v.oc, v.st, v.rays, v.raymask, v.rayoff, v.spts, v.ssdf, v.ray_alive, v.D);      // one wave per ray
 }
-void launch_jrows(const ObjConst* oc, const ObjState* st, const float4* jpts, const float2* jaux, const float* jgrad, const int* jrow, int term, float* rows,
-                  int cap, hipStream_t s) {
-    hipLaunchKernelGGL(k_jrows, dim3((cap + 255) / 256), dim3(256), 0, s, oc, st, jpts, jaux, jgrad, jrow, term, rows);
+#define PASS_ARGS(ps) (ps).j0, (ps).j1, (ps).n_depth, (ps).pass, (ps).last, (ps).hint, (ps).plo
+void launch_pass_list(const GnView& v, const PassSpec& ps) {
+    hipLaunchKernelGGL(k_pass_select, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ray_alive, v.pcnt, PASS_ARGS(ps));
+    scan_rays(v, 2);
+    hipLaunchKernelGGL(k_pass_write, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ray_alive, v.poff, v.plist, PASS_ARGS(ps));
 }
-void launch_solve(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int iter,
-                  float* trace, const float* codew, const float* b0, const float* blat, float* cbias, const float* depths_next, int B, hipStream_t s,
-                  const GroupEnt* grp, int* gmk, const StopRule* stop, const PriorDev* prior, const StepDev* step, const ObsWeightsDev* ow) {
-    const double* wn = ow ? (grp ? ow->gsums : ow->sums) : nullptr;
-    const StepDev sd = step ? *step : StepDev{};
-    const StopRule rule = stop ? *stop : StopRule{0.0, 0.0, 1};
-    const PriorDev pr = prior ? *prior : PriorDev{};
-    hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
-    if (!grp) {
-        if (prior) launch_prior_terms(st, prm, pr, nullptr, step ? 2 : 0, B, s);
-        auto k = prior ? (stop ? k_solve<false, true, true, false> : k_solve<false, false, true, false>)
-                       : (stop ? k_solve<false, true, false, false> : k_solve<false, false, false, false>);
-        if (step)
-            k = prior ? (stop ? k_solve<false, true, true, true> : k_solve<false, false, true, true>)
-                      : (stop ? k_solve<false, true, false, true> : k_solve<false, false, false, true>);
-        hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rule, pr, sd, wn);
-        return;
-    }
-    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, iter, trace, B,
-                       ow ? (const double*)ow->sums : nullptr, ow ? ow->gsums : nullptr);
-    if (prior) launch_prior_terms(st, prm, pr, grp, 0, B, s);
-    if (step) throw std::invalid_argument("step control is not built for multi-view batches");
-    auto k = prior ? (stop ? k_solve<true, true, true, false> : k_solve<true, false, true, false>)
-                   : (stop ? k_solve<true, true, false, false> : k_solve<true, false, false, false>);
-    hipLaunchKernelGGL(k, dim3(B), dim3(SOLVE_THREADS), 0, s, oc, st, gsum, prm, iter, codew, b0, blat, cbias, trace, depths_next, B, grp,
-                       (const int*)gmk, rule, pr, sd, wn);
-    launch_group_broadcast(grp, st, cbias, depths_next, prm.n_depth, B, s);
+void launch_pass_update(const GnView& v, int use_lp_delta, const PassSpec& ps) {
+    hipLaunchKernelGGL(k_pass_update, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ray_alive, v.ssdf, v.prm.cut_off, use_lp_delta,
+                       PASS_ARGS(ps));
 }
-void launch_prior_terms(ObjState* st, const GnParamsDev& prm, const PriorDev& pr, const GroupEnt* grp, int final_pass, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_prior_terms, dim3(B), dim3(PRIOR_THREADS), 0, s, st, prm, pr, grp, final_pass);
+void launch_band_select(const GnView& v, unsigned guard_salt) {
+    hipLaunchKernelGGL(k_band_count, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ssdf, v.prm.cut_off, guard_salt, v.pcnt);
+    scan_rays(v, 2);
+    hipLaunchKernelGGL(k_band_write, GRID_RAYS(v, 256), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ssdf, v.prm.cut_off, guard_salt, v.poff, v.plist);
 }
-void launch_posterior_park(ObjState* st, int* park, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_posterior_park, dim3((B + 63) / 64), dim3(64), 0, s, st, park, B);
+void launch_prepass_audit(const GnView& v) {
+    hipLaunchKernelGGL(k_prepass_audit, dim3(64, v.B), dim3(256), 0, v.s, v.oc, v.st, v.ssdf, v.saudit, v.prm.cut_off, v.summary + SUM_AUDIT);
 }
-void launch_posterior(const ObjConst* oc, ObjState* st, const float* partials, double* gsum, int n_slices, const GnParamsDev& prm, int weights, int level,
-                      const int* park, double* rec, int rec_stride, int B, hipStream_t s, const GroupEnt* grp, int* gmk, const PriorDev* prior,
-                      const ObsWeightsDev* ow) {
-    // the reductions launch_solve runs (no trace row), then the record
-    const double* wn = ow ? (grp ? ow->gsums : ow->sums) : nullptr;
-    const PriorDev pr = prior ? *prior : PriorDev{};
-    hipLaunchKernelGGL(k_gram_reduce, dim3((72 * 72 + 255) / 256, B, prm.pose_only ? 1 : 2), dim3(256), 0, s, st, partials, n_slices, gsum);
-    if (!grp) {
-        auto k = prior ? k_posterior<false, true> : k_posterior<false, false>;
-        hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park,
-                           (const GroupEnt*)nullptr, (const int*)nullptr, rec, rec_stride, pr, wn);
-        return;
-    }
-    hipLaunchKernelGGL(k_group_reduce, dim3((72 * 72 + 255) / 256, B, 2), dim3(256), 0, s, grp, oc, st, gsum, gmk, 0, (float*)nullptr, B,
-                       ow ? (const double*)ow->sums : nullptr, ow ? ow->gsums : nullptr);
-    auto k = prior ? k_posterior<true, true> : k_posterior<true, false>;
-    hipLaunchKernelGGL(k, dim3(B), dim3(POST_THREADS), 0, s, oc, st, (const double*)gsum, prm, weights, level, park, grp,
-                       (const int*)gmk, rec, rec_stride, pr, wn);
+void launch_front_wave(const GnView& v) {
+    const int nrb = std::max(1, (v.maxR + WAVE_RAYS - 1) / WAVE_RAYS), nsb = (v.maxM + WAVE_THREADS - 1) / WAVE_THREADS;
+    hipLaunchKernelGGL(k_front_wave, dim3((unsigned)(nrb + nsb), (unsigned)v.B), dim3(WAVE_THREADS), 0, v.s, v.oc, v.st, v.rays, v.pts, v.raymask, v.raycnt, v.rayoff,
+                       v.spts, v.ssdf, v.ray_alive, v.jpts, v.jaux, v.D, nrb, v.obs.ray_w);
 }
-void launch_group_broadcast(const GroupEnt* grp, ObjState* st, float* cbias, const float* depths, int n_depth, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_group_broadcast, dim3(B), dim3(64), 0, s, grp, st, cbias, depths, n_depth);
+void launch_band_wave(const GnView& v, unsigned guard_salt) {
+    const bool spec = v.srow != nullptr;      // a speculative plan: the band samples become jacobian rows at once
+    hipLaunchKernelGGL(k_band_wave, GRID_RAYS(v, WAVE_RAYS), dim3(WAVE_THREADS), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ssdf, v.prm.cut_off, guard_salt, v.plist,
+                       spec ? v.spts : nullptr, spec ? v.jpts : nullptr, v.srow);
 }
-void launch_inlier_filter(const ObjConst* oc, ObjState* st, const float* jgrad, unsigned char* alive, int maxM, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_inlier_filter, GRID2(maxM, B), dim3(256), 0, s, oc, st, jgrad, alive);
-    hipLaunchKernelGGL(k_count_alive, dim3(B), dim3(256), 0, s, oc, st, alive);
+void launch_render_tail_wave(const GnView& v) {
+    hipLaunchKernelGGL(k_render_tail_wave, GRID_RAYS(v, TAIL_RAYS), dim3(WAVE_THREADS), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.spts, v.sdeds, v.ray_res, v.kcnt,
+                       v.mcnt, v.jpts, v.jaux, v.srow, v.jrow, v.obs.ray_w, v.obs.jw);
 }
-void launch_finalize(ObjState* st, const float* scale, int B, int pose_only, float* packed, unsigned* guard_out, hipStream_t s, const GroupEnt* grp,
-                     unsigned* iters_out) {
-    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, st, scale, B, pose_only, packed, guard_out, grp, iters_out);
+void launch_surface(const GnView& v) {
+    hipLaunchKernelGGL(k_surface, GRID2(v.maxM, v.B), dim3(256), 0, v.s, v.oc, v.st, v.pts, v.jpts, v.jaux);
+}
+void launch_build_tiles(const GnView& v, int mode, int list, int add_v, int tile_pts, int cnt_slot, int apply_few) {
+    hipLaunchKernelGGL(k_build_tiles, dim3(1), dim3(256), 0, v.s, v.oc, v.st, v.B, mode, list == LIST_FWD ? v.tiles_f : v.tiles_j, v.n_tiles + list,
+                       reinterpret_cast<double*>(v.summary + SUM_COUNTERS), add_v, tile_pts, cnt_slot, apply_few);
+}
+void launch_render_scan(const GnView& v) {       // one wave per ray
+    hipLaunchKernelGGL(k_render_scan, GRID_RAYS(v, 4), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ssdf, v.depth, v.sdeds, v.ray_res, v.kcnt, v.mcnt, v.D,
+                       v.prm.cut_off);
+}
+void launch_report(const GnView& v) {
+    const GnParamsDev& prm = v.prm;
+    const ReportDev& rp = v.report;
+    if (!prm.pose_only && v.maxR > 0)      // one wave per ray
+        hipLaunchKernelGGL(k_report_rays, GRID_RAYS(v, 4), dim3(256), 0, v.s, v.oc, v.st, v.raymask, v.rayoff, v.ssdf, v.depth, prm.n_depth, prm.cut_off, rp.ray_depth,
+                           rp.ray_hit, rp.ray_residual, rp.ray_counts, v.obs.ray_w);
+    if (v.maxM > 0) hipLaunchKernelGGL(k_report_points, GRID2(v.maxM, v.B), dim3(256), 0, v.s, v.oc, v.st, v.jgrad, v.alive, rp.pt_sdf, rp.pt_flags);
+    // k_report_members puts the parked status words back where the posterior is off: nobody else will
+    hipLaunchKernelGGL(k_report_members, GRID_OBJ(v), dim3(256), 0, v.s, v.oc, v.st, v.jaux, v.jgrad, v.alive, prm.b2, prm.b1, prm.pose_only ? 0 : 1, prm.pose_only,
+                       v.post_level ? nullptr : v.park, rp.member, v.obs.pt_w, prm.pose_only ? nullptr : v.obs.jw);
+}
+void launch_render_tail(const GnView& v) {
+    scan_rays(v, 1);
+    hipLaunchKernelGGL(k_sum_m, GRID_OBJ(v), dim3(256), 0, v.s, v.oc, v.st, v.mcnt);
+    hipLaunchKernelGGL(k_render_write, GRID_RAYS(v, 4), dim3(256), 0, v.s, v.oc, v.st, v.raycnt, v.rayoff, v.koff, v.spts, v.sdeds, v.ray_res, v.jpts, v.jaux,
+                       v.obs.ray_w, v.obs.jw);      // one wave per ray
+}
+void launch_gram(const GnView& v) {
+    const int pose_only = v.prm.pose_only;
+    auto k = !v.weighted() ? k_gram<false> : k_gram<true>;     // weights off: the kernel without them, alone
+    hipLaunchKernelGGL(k, dim3(v.n_slices, v.B, pose_only ? 1 : 2), dim3(256), 0, v.s, v.oc, v.st, v.jpts, v.jaux, v.jgrad, v.jrow, v.alive, v.partials, v.n_slices,
+                       v.prm.b2, v.prm.b1, pose_only ? 0 : 1, v.obs.pt_w, v.obs.jw);
+    if (v.weighted()) hipLaunchKernelGGL(k_weight_sums, GRID_OBJ(v), dim3(256), 0, v.s, v.oc, v.st, v.obs.pt_w, v.obs.jw, v.alive, pose_only, v.obs.sums);
+}
+void launch_jrows(const GnView& v, int term, float* rows, int cap) {
+    hipLaunchKernelGGL(k_jrows, dim3((cap + 255) / 256), dim3(256), 0, v.s, v.oc, v.st, v.jpts, v.jaux, v.jgrad, v.jrow, term, rows);
+}
+// What k_solve and k_posterior start from: the slices summed per member and -- groups -- pooled at the leaders (trace, optional: the members' rows
+// of iteration iter).  Returns the weight sums their means divide by (null without observation weights).
+static const double* reduce_system(const GnView& v, int iter, float* trace) {
+    hipLaunchKernelGGL(k_gram_reduce, GRID_SYS(v, v.prm.pose_only ? 1 : 2), dim3(256), 0, v.s, v.st, v.partials, v.n_slices, v.gsum);
+    if (!v.grp) return v.obs.sums;
+    hipLaunchKernelGGL(k_group_reduce, GRID_SYS(v, 2), dim3(256), 0, v.s, v.grp, v.oc, v.st, v.gsum, v.gmk, iter, trace, v.B, v.obs.sums, v.obs.gsums);
+    return v.obs.gsums;
+}
+void launch_solve(const GnView& v, int iter, int last) {
+    const bool groups = v.grp != nullptr, stop = v.stops(), prior = v.has_prior(), step = v.step_control();
+    if (step && groups) throw std::invalid_argument("step control is not built for multi-view batches");
+    StepDev sd = v.step;
+    if (step) sd.last = last;
+    const float* depths_next = iter + 1 < v.sched_iters ? v.depth_sched + (size_t)(iter + 1) * v.B * MAX_DEPTH_SAMPLES : nullptr;
+    const double* wn = reduce_system(v, iter, v.trace);
+    if (prior) launch_prior_terms(v, step ? 2 : 0);
+    auto k = prior ? (stop ? k_solve<false, true, true, false> : k_solve<false, false, true, false>)
+                   : (stop ? k_solve<false, true, false, false> : k_solve<false, false, false, false>);
+    if (step)
+        k = prior ? (stop ? k_solve<false, true, true, true> : k_solve<false, false, true, true>)
+                  : (stop ? k_solve<false, true, false, true> : k_solve<false, false, false, true>);
+    if (groups)
+        k = prior ? (stop ? k_solve<true, true, true, false> : k_solve<true, false, true, false>)
+                  : (stop ? k_solve<true, true, false, false> : k_solve<true, false, false, false>);
+    hipLaunchKernelGGL(k,GRID_OBJ(v), dim3(SOLVE_THREADS), 0, v.s, v.oc, v.st, v.gsum, v.prm, iter, v.codew, v.b0, v.blat, v.cbias, v.trace, depths_next, v.B, v.grp,
+                       v.gmk, v.stop, v.prior, sd, wn);
+    if (groups) hipLaunchKernelGGL(k_group_broadcast, GRID_OBJ(v), dim3(64), 0, v.s, v.grp, v.st, v.cbias, depths_next, v.prm.n_depth);
+}
+void launch_prior_terms(const GnView& v, int final_pass) {
+    hipLaunchKernelGGL(k_prior_terms, GRID_OBJ(v), dim3(PRIOR_THREADS), 0, v.s, v.st, v.prm, v.prior, v.grp, final_pass);
+}
+void launch_posterior_park(const GnView& v) {
+    hipLaunchKernelGGL(k_posterior_park, GRID_OBJ64(v), dim3(64), 0, v.s, v.st, v.park, v.B);
+}
+void launch_posterior(const GnView& v) {
+    const double* wn = reduce_system(v, 0, nullptr);      // (no trace row), then the record
+    const bool prior = v.has_prior();
+    auto k = !v.grp ? (prior ? k_posterior<false, true> : k_posterior<false, false>) : (prior ? k_posterior<true, true> : k_posterior<true, false>);
+    hipLaunchKernelGGL(k, GRID_OBJ(v), dim3(POST_THREADS), 0, v.s, v.oc, v.st, v.gsum, v.prm, v.post_weights, v.post_level, v.park, v.grp, v.gmk, v.post_rec,
+                       v.post_stride, v.prior, wn);
+}
+void launch_group_broadcast(const GnView& v, bool start) {
+    hipLaunchKernelGGL(k_group_broadcast, GRID_OBJ(v), dim3(64), 0, v.s, v.grp, v.st, start ? nullptr : v.cbias, start ? v.depths_start : nullptr, v.D);
+}
+void launch_inlier_filter(const GnView& v) {
+    hipLaunchKernelGGL(k_inlier_filter, GRID2(v.maxM, v.B), dim3(256), 0, v.s, v.oc, v.st, v.jgrad, v.alive);
+    hipLaunchKernelGGL(k_count_alive, GRID_OBJ(v), dim3(256), 0, v.s, v.oc, v.st, v.alive);
+}
+void launch_finalize(const GnView& v) {
+    hipLaunchKernelGGL(k_finalize, GRID_OBJ64(v), dim3(64), 0, v.s, v.st, v.scale, v.B, v.prm.pose_only, v.packed, v.guard_on ? v.summary + SUM_GUARD : nullptr, v.grp,
+                       v.summary + sum_iters(v.B));      // (ObjState::n_iter of every member)
 }
 
 // Testing (dsp_debug_lie): the Lie-group maps and the rotation prior exactly as k_solve evaluates them -- ONE thread, the same device

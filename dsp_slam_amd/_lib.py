@@ -112,6 +112,8 @@ SYMBOLS = [
     ("dsp_debug_report_ray", C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_float, C.c_float, C.c_int, c_f32p, c_i32p]),
     ("dsp_batch_observation_weights", C.c_int, [_VP, c_f32p, c_f32p]),
     ("dsp_debug_observation_weights_check", C.c_int, [C.c_int64, C.c_int64, c_f32p, c_f32p]),
+    ("dsp_batch_unknowns", C.c_int, [_VP, C.POINTER(C.c_uint8)]),
+    ("dsp_debug_unknowns_check", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     ("dsp_sdf_jacobian_lp", C.c_int, [_VP, C.c_int, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p]),
     ("dsp_batch_set_debug", C.c_int, [_VP, C.c_int, C.c_int]),
     ("dsp_prepass_calibration", C.c_int, [_VP, C.c_int, c_f32p, c_f32p]),

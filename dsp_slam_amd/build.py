@@ -11,7 +11,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdspgn.so")
 SOURCES = ["mlp_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "gn_kernels.hip", "mesh_kernels.hip", "dsp_gn.hip",
            "pose_graph.cpp"]
-HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
+HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(CSRC, "gn_solve_body.h"), os.path.join(CSRC, "gn_posterior_body.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
            os.path.join(ROOT, "include", "dsp_pose_graph.h")]
 
 

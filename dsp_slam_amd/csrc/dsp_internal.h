@@ -393,6 +393,8 @@ struct GnView {
     StopRule stop{0.0, 0.0, 1};     // the convergence rule; off = a pose tolerance of 0, which can stop nothing
     StepDev step;                   // Levenberg-Marquardt step control (StepDev::last is set per launch)
     ReportDev report;
+    const unsigned char* live = nullptr;    // mask of unknowns (dsp_batch_unknowns): 71 bytes per OBJECT (pose-only 6), 1 = live; on: the masked k_solve / k_posterior
+    bool masked() const { return live != nullptr; }
     bool weighted() const { return obs.sums != nullptr; }
     bool has_prior() const { return prior.extra != nullptr; }
     bool stops() const { return stop.pose_tol > 0.0; }

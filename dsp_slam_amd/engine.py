@@ -31,6 +31,28 @@ def params_from_configs(configs):
                      get(o, "num_depth_samples"), get(o, "cut_off_threshold"), pose_it)
 
 
+# ---- mask of unknowns (dsp_batch_unknowns, include/dsp_gn.h): named groups of H's order [v(3), w(3), sigma | code(64)] ---------------------
+UNKNOWN_GROUPS = {"translation": (0, 1, 2), "rotation": (3, 4, 5), "yaw": (4,), "scale": (6,), "pose": tuple(range(7)), "code": tuple(range(7, 71)),
+                  "all": tuple(range(71))}
+
+
+def unknowns_mask(groups, pose_only=False):
+    """The LIVE groups -> a uint8 mask (71,), pose-only (6,): 1 = live, 0 = frozen.  groups: one name or a list of names out of "translation"
+    (entries 0-2), "rotation" (3-5), "yaw" (4 only: the rotation about the object's up axis), "scale" (6), "pose" (0-6), "code" (7-70), "all".
+    An empty list freezes everything.  A pose-only batch has the six SE(3) entries: "scale" and "code" name nothing there, "pose" and "all" are
+    its six.  An unknown name raises ValueError."""
+    if isinstance(groups, str):
+        groups = [groups]
+    n = 6 if pose_only else 71
+    m = np.zeros(n, np.uint8)
+    for g in groups:
+        if g not in UNKNOWN_GROUPS:
+            raise ValueError("unknowns: no group %r (known: %s)" % (g, ", ".join(sorted(UNKNOWN_GROUPS))))
+        idx = [i for i in UNKNOWN_GROUPS[g] if i < n]
+        m[idx] = 1
+    return m
+
+
 def _ragged(arrays, width):
     """list of (n_i, width) arrays -> (offsets int64 (B+1), flat float32 (sum n_i, width))."""
     arrays = [L.f32(a).reshape(-1, width) if width else L.f32(a).reshape(-1) for a in arrays]
@@ -228,6 +250,34 @@ class Batch(object):
         pw = flat(pt_w, n_p.value, "pt_w")
         rw = None if self.pose_only else flat(ray_w, n_r.value, "ray_w")
         L.check(lib.dsp_batch_observation_weights(self._h, L.ptr(pw), L.ptr(rw)), h, "dsp_batch_observation_weights")
+
+    # ---- mask of unknowns (dsp_batch_unknowns, include/dsp_gn.h): which pose, scale and code entries the following runs estimate -------------
+    def set_unknowns(self, live=None):
+        """live: None = every entry live = off (the initial state); an (n, 71) array (pose-only batch: (n, 6)) of 1 = live / 0 = frozen in H's
+        order [v(3), w(3), sigma | code(64)], or one (71,) / (6,) row for every object; or group names (unknowns_mask): a list of names for the
+        whole batch, or a list of n lists, one per object.  Frozen entries keep their value: the run solves the system conditioned on them.
+        The mask stays set for the following runs.  Multi-view batches take it per object."""
+        lib, h = L.load(), self.engine._h
+        if live is None:
+            L.check(lib.dsp_batch_unknowns(self._h, None), h, "dsp_batch_unknowns")
+            return
+        w = 6 if self.pose_only else 71
+        if isinstance(live, str):
+            live = [live]
+        if isinstance(live, (list, tuple)) and (len(live) == 0 or all(isinstance(x, str) for x in live)):
+            m = unknowns_mask(live, self.pose_only)
+        elif isinstance(live, (list, tuple)) and all(isinstance(x, (list, tuple, str)) and (isinstance(x, str) or all(isinstance(y, str) for y in x))
+                                                     for x in live):
+            m = np.stack([unknowns_mask(x, self.pose_only) for x in live])
+        else:
+            m = np.asarray(live)
+            m = np.where((m == 0) | (m == 1), m, 2).astype(np.uint8)         # anything else reaches the library as 2, which it refuses
+        if m.ndim == 1 and m.shape[0] == w:
+            m = np.broadcast_to(m, (self.n, w))
+        if m.shape != (self.n, w):
+            raise ValueError("set_unknowns: the mask must be (%d, %d) or (%d,), not %r" % (self.n, w, w, tuple(m.shape)))
+        m = np.ascontiguousarray(m, np.uint8)
+        L.check(lib.dsp_batch_unknowns(self._h, L.ptr(m, C.POINTER(C.c_uint8))), h, "dsp_batch_unknowns")
 
     def _member_offsets(self, n_members):
         """pts_off / ray_off / depth_off per member as they were uploaded, and view_off (every object one member)."""
@@ -828,7 +878,7 @@ class Engine(object):
         return Batch(self, prm, t_co_se3, pts, None, None, codes, trace, scale=scale)
 
     def reconstruct_batch(self, prm, t_cam_obj, pts, rays, depth, codes=None, compute=L.COMPUTE_F32, convergence=None, step_control=None, posterior=None,
-                          obs_weights=None, report=None, prior=None):
+                          unknowns=None, obs_weights=None, report=None, prior=None):
         """compute: L.COMPUTE_F32 (default, the parity path) or the opt-in low-precision mode L.COMPUTE_F16 / _BF16 (dsp_batch_set_compute).
         convergence: None (every object runs every iteration) or (pose_tol, code_tol[, min_iterations]) -- Batch.set_convergence.
         posterior: None, "mean" / "sum" or (level, weights) -- Batch.set_posterior; the call then returns a fifth item, Batch.posterior()
@@ -839,7 +889,8 @@ class Engine(object):
         lambda_min, lambda_max) tuple; the returned items are the same, `loss` is then the loss AT the returned state.
         report: None / False, or True -- Batch.set_report; the call then returns Batch.report() behind the posterior (in front of the prior's
         residual, which stays last).
-        obs_weights: None, or (pt_w, ray_w) -- Batch.set_observation_weights; the returned items are the same."""
+        obs_weights: None, or (pt_w, ray_w) -- Batch.set_observation_weights; the returned items are the same.
+        unknowns: None, or what Batch.set_unknowns takes (a mask, or the names of the live groups); the returned items are the same."""
         if len(pts) == 0:      # an empty shard (more ranks than objects): nothing to run, but the caller still joins the gather
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
             return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
@@ -847,6 +898,8 @@ class Engine(object):
         try:
             if compute != L.COMPUTE_F32:
                 b.set_compute(compute)
+            if unknowns is not None:
+                b.set_unknowns(unknowns)
             return _run_resident(b, convergence, posterior, prior, step_control, report, obs_weights)
         finally:
             b.close()
@@ -855,18 +908,21 @@ class Engine(object):
         """Device-resident multi-view batch: views[i] = the list of dict(t_ref_cam, pts, rays, depth) of object i (MultiviewBatch)."""
         return MultiviewBatch(self, prm, t_cam_obj, views, codes, trace)
 
-    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, obs_weights=None, report=None, prior=None):
+    def reconstruct_multiview_batch(self, prm, t_cam_obj, views, codes=None, convergence=None, posterior=None, unknowns=None, obs_weights=None, report=None,
+                                    prior=None):
         """dsp_reconstruct_multiview: one pose and one code per object from all its views -> (t_cam_obj, code, loss, status) per object.
         convergence: (pose_tol, code_tol[, min_iterations]) runs a resident batch with that rule (Batch.set_convergence) instead of the one-shot call.
         posterior, report, prior: as reconstruct_batch (a resident batch too; further items, per object -- the report's rows per VIEW).
-        obs_weights: as reconstruct_batch, per VIEW (a resident batch too)."""
+        obs_weights: as reconstruct_batch, per VIEW (a resident batch too).  unknowns: as reconstruct_batch, per OBJECT (a resident batch too)."""
         n = len(views)
         if n == 0:
             empty = (np.zeros((0, 4, 4), np.float32), np.zeros((0, self.code_len), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
             return empty + (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
-        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None:
+        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None or unknowns is not None:
             b = MultiviewBatch(self, prm, t_cam_obj, views, codes)
             try:
+                if unknowns is not None:
+                    b.set_unknowns(unknowns)
                 return _run_resident(b, convergence, posterior, prior, None, report, obs_weights)
             finally:
                 b.close()
@@ -883,19 +939,22 @@ class Engine(object):
                                                    L.ptr(code), L.ptr(loss), L.ptr(status, L.c_i32p)), self._h, "dsp_reconstruct_multiview")
         return t_out, np.ascontiguousarray(code[:, :self.code_len]), loss, status
 
-    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, obs_weights=None, report=None, prior=None):
+    def estimate_pose_batch(self, prm, t_co_se3, scale, pts, codes, convergence=None, posterior=None, unknowns=None, obs_weights=None, report=None, prior=None):
         """convergence: (pose_tol, code_tol[, min_iterations]) (code_tol is ignored) runs a resident pose batch with that rule instead of the
         one-shot call.  posterior: as reconstruct_batch (a resident batch too); the call then returns (poses, Batch.posterior()).
         report: as reconstruct_batch; Batch.report() follows the posterior (the alive bits are the inlier filter's mask).
         prior: as reconstruct_batch, with (6, 6) Lambdas and t_obj_cam0 carrying the scale; Batch.prior_residual() is then the last item.
-        obs_weights: as reconstruct_batch (a resident batch too); the ray weights are ignored."""
+        obs_weights: as reconstruct_batch (a resident batch too); the ray weights are ignored.
+        unknowns: as reconstruct_batch, with (n, 6) masks or the pose groups (a resident batch too)."""
         n = len(pts)
         if n == 0:
             extra = (() if posterior is None else ({},)) + (({},) if report else ()) + (() if prior is None else ({},))
             return np.zeros((0, 4, 4), np.float32) if not extra else (np.zeros((0, 4, 4), np.float32),) + extra
-        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None:
+        if convergence is not None or posterior is not None or prior is not None or report or obs_weights is not None or unknowns is not None:
             b = self.pose_batch(prm, t_co_se3, scale, pts, codes)
             try:
+                if unknowns is not None:
+                    b.set_unknowns(unknowns)
                 res = _run_resident(b, convergence, posterior, prior, None, report, obs_weights)
                 return res[0] if len(res) == 4 else (res[0],) + res[4:]
             finally:

@@ -121,6 +121,28 @@ class Optimizer(object):
         except TypeError:
             pass
 
+        # ADDITION (not in the reference's configs): "unknowns": [group, ...] under "joint_optim" / "pose_only_optim" names the LIVE groups of
+        # unknowns (dsp_batch_unknowns; dsp_slam_amd.engine.unknowns_mask: translation, rotation, yaw, scale, pose, code, all); every other
+        # entry is frozen at its start value.  Read with a membership test like the keys above; absent means every entry is live.  An
+        # unknown name raises ValueError here, not at the first call.
+        def optional_groups(block, pose_only):
+            try:
+                g = block["unknowns"] if "unknowns" in block else None
+            except TypeError:
+                return None
+            if g is None:
+                return None
+            g = [g] if isinstance(g, str) else [str(x) for x in g]
+            _engine.unknowns_mask(g, pose_only)
+            return g
+        self.unknowns_joint = optional_groups(joint, False)
+        self.unknowns_pose_only = None
+        try:
+            if "pose_only_optim" in optim_cfg:
+                self.unknowns_pose_only = optional_groups(optim_cfg["pose_only_optim"], True)
+        except TypeError:
+            pass
+
     def _params(self):
         return _engine.gn_params(self.k1, self.k2, self.k3, self.k4, self.b1, self.b2, self.lr, self.s_damp,
                                  self.num_iterations_joint_optim, self.num_depth_samples, self.cut_off,
@@ -154,14 +176,18 @@ class Optimizer(object):
                 rw.append(np.ones(len(rays_list[i]), np.float32) if r is None else _f32(r).reshape(-1))
         return pw, (rw if rays_list is not None else None)
 
-    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes, return_posterior=False, obs_weights=None, priors=None):
+    def estimate_poses_cam_obj(self, t_co_se3_list, scales, pts_list, codes, return_posterior=False, unknowns=None, obs_weights=None, priors=None):
         """Batched form: lists of per-object inputs -> (B,4,4) float32 array of optimised SE(3) poses.  return_posterior=True: (poses,
         Batch.posterior() dict) -- 6 x 6 pose information / covariance per object, with the weights of pose_only_optim.posterior ("mean" if absent).
         priors: None, or one dict(t_obj_cam (4, 4) with the scale in it, Lambda (6, 6)) or None per object (dsp_batch_prior); the call then
         returns Batch.prior_residual() as its last item.  With pose_only_optim.report set the call returns Batch.report() (per-point sdf and
         the inlier filter's alive bits) behind the posterior, in front of the prior's residual.  obs_weights: None, or one (pt_w, None) or
-        None per object -- per-point weights (dsp_batch_observation_weights)."""
+        None per object -- per-point weights (dsp_batch_observation_weights).  unknowns: None (pose_only_optim.unknowns, or every entry), or
+        what Batch.set_unknowns takes: the names of the live groups, or an (n, 6) mask (dsp_batch_unknowns)."""
         kw = {} if self.convergence_pose_only is None else {"convergence": self.convergence_pose_only}
+        unknowns = self.unknowns_pose_only if unknowns is None else unknowns
+        if unknowns is not None:
+            kw["unknowns"] = unknowns
         if obs_weights is not None:
             kw["obs_weights"] = self._stack_obs_weights(obs_weights, pts_list, None)
         if return_posterior:
@@ -173,18 +199,20 @@ class Optimizer(object):
         return self.decoder.engine.estimate_pose_batch(self._params(), [_f32(t) for t in t_co_se3_list], scales,
                                                        [_f32(p) for p in pts_list], [_f32(c) for c in codes], **kw)
 
-    def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code, obs_weights=None, prior=None):
+    def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code, unknowns=None, obs_weights=None, prior=None):
         """Pose-only refinement of one detection (reference optimizer.py:45-86; called from LocalMapping_util.cc:109-110).
         t_co_se3: (4, 4) rigid object-to-camera guess; scale: the object's scale (float); pts: (M, 3) surface points in the camera frame;
         code: the object's shape code.  Returns the refined rigid object-to-camera matrix as a (4, 4) CPU torch.Tensor, like the reference.
         prior (an addition): dict(t_obj_cam, Lambda (6, 6)) -- the last estimate of this object and its information (one row of a pose-only
         Batch.posterior() at level 2); the call then returns a dict: t_cam_obj (the tensor), prior_chi2, prior_residual (6,).
-        obs_weights (an addition): (pt_w, None) -- one weight per surface point; the return value is what it is without them."""
+        obs_weights (an addition): (pt_w, None) -- one weight per surface point; the return value is what it is without them.
+        unknowns (an addition): the names of the live groups, e.g. ["translation", "yaw"], or a (6,) mask; the return value is what it is."""
         ow = None if obs_weights is None else [obs_weights]
         if prior is None and not self.report_pose_only:
-            out = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], obs_weights=ow)
+            out = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], unknowns=unknowns, obs_weights=ow)
             return torch.from_numpy(out[0].copy())
-        ret = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], obs_weights=ow, priors=None if prior is None else [prior])
+        ret = self.estimate_poses_cam_obj([t_co_se3], [float(scale)], [pts], [code], unknowns=unknowns, obs_weights=ow,
+                                          priors=None if prior is None else [prior])
         extra = {}
         if self.report_pose_only:       # (an addition, like the prior: the call then returns a dict)
             extra["observations"] = _observations.object_rows(ret[1], 0)
@@ -193,10 +221,12 @@ class Optimizer(object):
         return ForceKeyErrorDict(t_cam_obj=torch.from_numpy(ret[0][0].copy()), **extra)
 
     # ---- joint shape + pose (reference optimizer.py:88-203) -----------------------------------------
-    def reconstruct_objects(self, t_cam_obj_list, pts_list, rays_list, depth_list, codes=None, obs_weights=None, priors=None):
+    def reconstruct_objects(self, t_cam_obj_list, pts_list, rays_list, depth_list, codes=None, unknowns=None, obs_weights=None, priors=None):
         """Batched form: B independent objects in one device run -> list of result dicts.  priors: None, or one dict(t_obj_cam, code,
         Lambda (71, 71)) or None per object (dsp_batch_prior); good objects then carry prior_chi2 and prior_residual.  obs_weights: None, or
-        one (pt_w, ray_w) or None per object (dsp_batch_observation_weights); the result dicts keep their keys."""
+        one (pt_w, ray_w) or None per object (dsp_batch_observation_weights); the result dicts keep their keys.  unknowns: None
+        (joint_optim.unknowns, or every entry), or what Batch.set_unknowns takes: the names of the live groups for the whole batch, one list
+        of names per object, or an (n, 71) mask (dsp_batch_unknowns); the result dicts keep their keys."""
         B = len(pts_list)
         codes_in = None
         if codes is not None:
@@ -212,6 +242,9 @@ class Optimizer(object):
             kw["report"] = True
         if obs_weights is not None:
             kw["obs_weights"] = self._stack_obs_weights(obs_weights, pts_list, rays_list)
+        unknowns = self.unknowns_joint if unknowns is None else unknowns
+        if unknowns is not None:
+            kw["unknowns"] = unknowns
         res = self.decoder.engine.reconstruct_batch(
             self._params(), [_f32(x) for x in t_cam_obj_list], [_f32(p) for p in pts_list],
             [_f32(r) for r in rays_list], [_f32(d).reshape(-1) for d in depth_list], codes_in, compute=self.compute, **kw)
@@ -248,29 +281,31 @@ class Optimizer(object):
             return {}
         return dict(prior_chi2=float(res[-1]["chi2"][i]), prior_residual=res[-1]["e"][i].copy())
 
-    def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None, obs_weights=None, prior=None):
+    def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None, unknowns=None, obs_weights=None, prior=None):
         """Joint shape + pose optimisation of one object (reference optimizer.py:88-203; LocalMapping_util.cc:179-180,391-392,402-403).
         t_cam_obj: (4, 4) Sim(3) object-to-camera start; pts: (M, 3) surface points in the camera frame; rays: (R, 3) ray directions, the
         first len(depth) of them foreground; depth: observed depth of the foreground rays (KITTI: one per surface point); code: optional
         start code (zeros when None).  Returns the reference's result dict: t_cam_obj, code, is_good, loss -- attribute access, KeyError on
         anything else.  prior (an addition): dict(t_obj_cam, code, Lambda (71, 71)) -- one row of a level-2 Batch.posterior() can be passed
         as it is -- fuses that earlier estimate into the run (dsp_batch_prior); the result then also has prior_chi2 and prior_residual.
-        obs_weights (an addition): (pt_w, ray_w), one weight per surface point / per ray, either None = ones; the result keeps its keys."""
+        obs_weights (an addition): (pt_w, ray_w), one weight per surface point / per ray, either None = ones; the result keeps its keys.
+        unknowns (an addition): the names of the live groups -- ["pose"] tracks the pose from points and rays with the code held, ["code"]
+        refits the shape under a fixed pose, ["translation", "rotation", "code"] keeps a known scale -- or a (71,) mask; same keys."""
         start = get_time()
-        rst = self.reconstruct_objects([t_cam_obj], [pts], [rays], [depth], None if code is None else [code],
-                                       None if obs_weights is None else [obs_weights], None if prior is None else [prior])[0]
+        rst = self.reconstruct_objects([t_cam_obj], [pts], [rays], [depth], None if code is None else [code], unknowns=unknowns,
+                                       obs_weights=None if obs_weights is None else [obs_weights], priors=None if prior is None else [prior])[0]
         if self.verbose and rst.is_good:
             print("Reconstruction takes %f seconds" % (get_time() - start))
         return rst
 
-    def reconstruct_object_multiview(self, t_cam_obj, views, code=None, obs_weights=None, prior=None):
+    def reconstruct_object_multiview(self, t_cam_obj, views, code=None, unknowns=None, obs_weights=None, prior=None):
         """Joint shape + pose optimisation of one object from SEVERAL observations (an addition: the reference's reconstruct_object,
         optimizer.py:88-203, takes one, although its map keeps one per key frame).  t_cam_obj: (4, 4) Sim(3) object-to-camera start in the
         frame of the REFERENCE camera = the camera of views[0]; views: [dict(t_ref_cam, pts, rays, depth), ...] -- t_ref_cam (4, 4) rigid,
         that view's camera -> the reference camera (identity for views[0]); pts / rays / depth as reconstruct_object takes them, in that
         view's camera frame.  All views share one pose and one code; their rows are pooled into one Gauss-Newton system per iteration.
         Same result dict as reconstruct_object; one view gives reconstruct_object's result, bit for bit.  prior: as reconstruct_object.
-        obs_weights: None, or one (pt_w, ray_w) or None per VIEW."""
+        obs_weights: None, or one (pt_w, ray_w) or None per VIEW.  unknowns: as reconstruct_object (one mask for the object, not per view)."""
         vs = [dict(t_ref_cam=_f32(v["t_ref_cam"]), pts=_f32(v["pts"]), rays=_f32(v["rays"]), depth=_f32(v["depth"]).reshape(-1)) for v in views]
         codes_in = None if code is None else [_f32(code)[:self.code_len]]
         kw = {} if self.convergence_joint is None else {"convergence": self.convergence_joint}
@@ -283,6 +318,9 @@ class Optimizer(object):
             kw["report"] = True
         if obs_weights is not None:
             kw["obs_weights"] = self._stack_obs_weights(obs_weights, [v["pts"] for v in vs], [v["rays"] for v in vs])
+        unknowns = self.unknowns_joint if unknowns is None else unknowns
+        if unknowns is not None:
+            kw["unknowns"] = unknowns
         res = self.decoder.engine.reconstruct_multiview_batch(self._params(), [_f32(t_cam_obj)], [vs], codes_in, **kw)
         t, z, loss, status = res[:4]
         if status[0] == _L.OBJ_GOOD:

@@ -551,6 +551,36 @@ int dsp_batch_observation_weights(dsp_batch* b, const float* pt_w, const float* 
 /* Testing (host only, no device): dsp_batch_observation_weights' checks on n_points / n_rays values (NULL = all ones: nothing to check). */
 int dsp_debug_observation_weights_check(int64_t n_points, int64_t n_rays, const float* pt_w, const float* ray_w);
 
+/* ---- mask of unknowns (optional): which of an object's pose, scale and code entries a run estimates ------------------------------------------
+ * live: n_objects x 71 bytes in H's order [v(3), w(3), sigma | code(64)] (a pose-only batch: n_objects x 6), 1 = live, 0 = frozen; a
+ * multi-view batch takes it per OBJECT, not per view.  NULL = every entry live = off (initial): the run launches the kernels of a batch that
+ * never had a mask and returns the same bits, and so does a mask of ones.  Entries at or beyond 7 + code_len of a 32-D decoder are not looked
+ * at (those slots stay pinned as they are).  The mask is copied to the device (the array comes from the handle's pool the first time:
+ * DSP_E_NOMEM leaves the mask off and the batch usable) and stays set for every following run, the partial re-run after a prepass-guard trip
+ * included, until changed.
+ * Frozen entries are NOT unknowns: the system is conditioned on their current value.  Behind everything else the solve step adds to its
+ * system -- data terms, k3, k4, a prior's block, the damping -- row and column i of H of a frozen index i are set to zero, H_ii = 1 and
+ * b_i = 0; that is the system the trace records and step control saves, and step control's lambda is not added to a frozen diagonal.  The
+ * pivot-free elimination then returns dx_i == 0.0 exactly and gives the live block the arithmetic of the reduced system in the same pivot
+ * order ("Mask of unknowns").  A frozen code entry keeps its bits; with every pose entry frozen (7; pose-only 6) the pose update is
+ * skipped, so t_obj_cam, the depth samples and everything else derived from the pose keep their bits across iterations.  The update is a
+ * left perturbation in the object frame: with w_x and w_z frozen the rotation is a pure yaw and the object's up axis keeps its direction in
+ * the camera frame -- the hard form of the k4 prior, which can then be 0.  An object with no live unknown is allowed: its run evaluates and
+ * moves nothing, `loss` is the loss at the start state.
+ *   convergence rule   a frozen entry's step is 0 and blocks no stop; an object with no live unknown converges at min_iterations
+ *   prior              entries of J^T Lp J and -J^T Lp e in a frozen row or column are not added (conditioning); e and chi2 of
+ *                      dsp_batch_prior_fetch stay the full residual
+ *   posterior          Lambda and g (level 2) have zeros in frozen rows and columns; info_pose is the Schur complement over the LIVE code
+ *                      entries on the live pose entries, cov_pose its inverse on that sub-block, zeros elsewhere (no live pose entry: both all
+ *                      zero, status DSP_POSTERIOR_OK); var_code is 0 at frozen entries; the singularity rule looks at live pivots only
+ * The report, observation weights, the low-precision compute mode, step control and every launch form work as without a mask.  NO decoder or
+ * Gram work is skipped for frozen entries: a masked run costs what the plain run costs (skipping the code columns of a code-frozen batch is
+ * a possible follow-up).  DSP_E_ARG (the previous mask stays): a value other than 0 or 1, a stale token.  The one-shot calls have no mask.
+ * (Not named dsp_batch_set_*: see dsp_batch_convergence.) */
+int dsp_batch_unknowns(dsp_batch* b, const uint8_t* live);
+/* Testing (host only, no device): dsp_batch_unknowns' argument checks for n_objects objects of a batch kind. */
+int dsp_debug_unknowns_check(int pose_only, int code_len, int n_objects, const uint8_t* live);
+
 /* ---- testing: ONE door for the forms the library chooses between by itself-----------------------------------------------------------
  * The launch sequence has several bit-identical forms per stage, chosen from the batch's size.  Tests pin a form to
  * compare it with the one it replaces; an integrator has no reason to.  value: -1 automatic, 0 off, 1 on where applicable, unless noted. */

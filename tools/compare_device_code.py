@@ -2,6 +2,7 @@
 """Is the gfx950 device code of two source trees the same?  (No GPU needed.)
 
     python tools/compare_device_code.py TREE_A TREE_B
+    python tools/compare_device_code.py --kernels TREE_A TREE_B
 
 For every .hip file under dsp_slam_amd/csrc of either tree: compile it device-only with the flags dsp_slam_amd/build.py uses for that file,
 unbundle the gfx950 code object, and compare
@@ -9,6 +10,11 @@ unbundle the gfx950 code object, and compare
   * the sha256 of the code object's metadata note (kernel names, per-kernel register / LDS / scratch figures, argument layouts).
 The bundle as a whole is NOT comparable: its module id is hashed from the input path.  Nothing here looks inside a section; it is a plain
 hash comparison.  Prints one line per file and section and exits 1 on any difference.
+
+--kernels: per KERNEL instead of per file -- for a change that ADDS kernels to a file and must leave the existing ones alone.  For every
+function symbol of the code object: the sha256 of its own bytes of .text (kernels here are self-contained: every call is inlined, branches
+are relative) and of its kernel descriptor (registers, LDS, scratch).  Prints the kernels that differ or exist in one tree only, and a
+count of the equal ones; exits 1 if a kernel of TREE_A is missing from TREE_B or differs there (kernels only TREE_B has are listed, not errors).
 """
 import hashlib
 import importlib.util
@@ -74,6 +80,60 @@ def device_hashes(tree, src, work):
     return out
 
 
+def kernel_hashes(tree, src, work):
+    """{kernel name: sha256 of its .text bytes + its descriptor} of one .hip file's gfx950 code object"""
+    device_hashes(tree, src, work)                      # leaves the code object in work/dev.co
+    co = os.path.join(work, "dev.co")
+    secs = {}
+    for line in _run([_tool("llvm-readelf"), "-S", "-W", co]).decode().splitlines():
+        f = line.replace("[", " ").replace("]", " ").split()
+        if len(f) >= 6 and f[1] in (".text", ".rodata"):
+            secs[f[1]] = (int(f[3], 16), int(f[4], 16), int(f[5], 16))      # address, file offset, size
+    blob = open(co, "rb").read()
+    syms = {}
+    for line in _run([_tool("llvm-readelf"), "-s", "-W", co]).decode().splitlines():
+        f = line.split()            # Num: Value Size Type Bind Vis Ndx Name
+        if len(f) == 8 and f[0].endswith(":") and f[3] in ("FUNC", "OBJECT") and f[6] != "UND":
+            syms[f[7]] = (int(f[1], 16), int(f[2], 0), f[3])
+    out = {}
+    for name, (addr, size, kind) in syms.items():
+        if kind != "FUNC" or ".text" not in secs:
+            continue
+        a0, off, _ = secs[".text"]
+        hsh = hashlib.sha256(blob[off + addr - a0: off + addr - a0 + size])
+        kd = syms.get(name + ".kd")
+        if kd and ".rodata" in secs:
+            r0, roff, _ = secs[".rodata"]
+            desc = bytearray(blob[roff + kd[0] - r0: roff + kd[0] - r0 + kd[1]])
+            desc[16:24] = bytes(8)                      # the entry's offset from the descriptor: where the kernel sits, not what it is
+            hsh.update(bytes(desc))
+        out[name] = hsh.hexdigest()
+    return out
+
+
+def main_kernels(a, b):
+    bad = 0
+    for src in sorted(f for f in os.listdir(os.path.join(a, "dsp_slam_amd", "csrc")) if f.endswith(".hip")):
+        if not os.path.exists(os.path.join(b, "dsp_slam_amd", "csrc", src)):
+            print("%-24s only in %s" % (src, a))
+            bad += 1
+            continue
+        with tempfile.TemporaryDirectory() as wa, tempfile.TemporaryDirectory() as wb:
+            ka, kb = kernel_hashes(a, src, wa), kernel_hashes(b, src, wb)
+        same = [k for k in ka if kb.get(k) == ka[k]]
+        for k in sorted(ka):
+            if k not in kb:
+                print("%-24s MISSING in second tree: %s" % (src, k))
+                bad += 1
+            elif kb[k] != ka[k]:
+                print("%-24s DIFFERS: %s" % (src, k))
+                bad += 1
+        for k in sorted(set(kb) - set(ka)):
+            print("%-24s new in second tree: %s" % (src, k))
+        print("%-24s %d of %d kernels of the first tree unchanged" % (src, len(same), len(ka)))
+    return 1 if bad else 0
+
+
 def main(a, b):
     def hips(t):
         return {f for f in os.listdir(os.path.join(t, "dsp_slam_amd", "csrc")) if f.endswith(".hip")}
@@ -93,6 +153,8 @@ def main(a, b):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--kernels":
+        sys.exit(main_kernels(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3])))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])))

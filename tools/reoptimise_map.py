@@ -120,7 +120,7 @@ def prior_arrays(prior, objs, obs, idx):
 
 
 def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=None, posterior=None, posterior_level=1, prior=None,
-               step_control=None, report=False, reject=None):
+               step_control=None, report=False, reject=None, unknowns=None):
     """objs / obs as read; engines: one dsp_slam_amd.engine.Engine per GPU.  -> (objects with updated pose / code, stats dict).
     shards: optional explicit (start, stop) blocks over the objects that have observations (default: cost-balanced over the engines).
     compute: 0 = fp32 (the parity path), 1 / 2 = the opt-in f16 / bf16 compute mode (include/dsp_gn.h: dsp_batch_set_compute).
@@ -137,9 +137,15 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
     numpy.savez takes them.
     reject: None, or (pt_sdf_max, ray_res_max): every shard runs with the report, turns it into 0 / 1 observation weights
     (observations.reject, Batch.set_observation_weights) and runs again on the same resident batch; everything returned is the second
-    run's, and stats["rejected"] holds (points, rays) given weight 0, counted over all observed objects."""
+    run's, and stats["rejected"] holds (points, rays) given weight 0, counted over all observed objects.
+    unknowns: None, or the names of the LIVE groups of unknowns (dsp_slam_amd.engine.unknowns_mask: translation, rotation, yaw, scale, pose,
+    code, all) -- Batch.set_unknowns; every other entry of every object keeps its value: ["pose"] tracks the poses with the map's codes
+    held, ["code"] refits the shapes under the map's poses."""
     from dsp_slam_amd import distributed as D
     from dsp_slam_amd import observations as OBS
+    if unknowns is not None:
+        from dsp_slam_amd.engine import unknowns_mask
+        unknowns_mask(list(unknowns))          # an unknown group name raises here, in front of any upload
     idx = [i for i, ob in enumerate(obs) if ob is not None]
     t_in, codes_in = [], []
     for i in idx:
@@ -168,7 +174,7 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
         a, b = shards[r]
         sel = idx[a:b]
         eng = engines[r % len(engines)]
-        if (tol is not None or posterior is not None or pri is not None or step_control is not None or report or reject is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
+        if (tol is not None or posterior is not None or pri is not None or step_control is not None or report or reject is not None or unknowns is not None) and b > a:      # the rule and the posterior live on resident batches: one per shard, created and destroyed here
             if multiview:
                 bt = eng.multiview_batch(prm, t_in[a:b], [views[i] for i in sel], codes_in[a:b])
             else:
@@ -186,6 +192,8 @@ def reoptimise(engines, prm, objs, obs, code_len, shards=None, compute=0, tol=No
                     bt.set_step_control(*step_control)
                 if report or reject is not None:
                     bt.set_report(True)
+                if unknowns is not None:
+                    bt.set_unknowns(list(unknowns))
                 bt.run()
                 if reject is not None:      # report -> weights -> the same batch once more
                     pt_w, ray_w = OBS.reject(bt.report(), reject[0], reject[1])
@@ -294,6 +302,9 @@ def main():
                          "depth / hit / residual / counts, per-view sums (dsp_slam_amd.observations reads them)")
     ap.add_argument("--reject", type=float, nargs=2, metavar=("PT_SDF", "RAY_RES"), default=None,
                     help="run twice on the same resident batch: observations whose |sdf| / |depth residual| at the first result exceed these bounds get weight 0 in the second")
+    ap.add_argument("--unknowns", default=None, metavar="GROUP[,GROUP...]",
+                    help="the LIVE groups of unknowns out of translation, rotation, yaw, scale, pose, code, all; every other entry keeps the map's value "
+                         "(pose: track the poses with the codes held; code: refit the shapes under the map's poses); every entry without the flag")
     args = ap.parse_args()
     from reconstruct.utils import get_configs
     from deep_sdf.workspace import config_decoder
@@ -309,7 +320,8 @@ def main():
                          tol=None if args.tol is None else tuple(args.tol), posterior=None if args.posterior is None else "sum",
                          posterior_level=args.posterior_level, prior=None if args.prior is None else dict(np.load(args.prior)),
                          step_control=None if args.step_control is None else tuple(args.step_control),
-                         report=args.report is not None, reject=None if args.reject is None else tuple(args.reject))
+                         report=args.report is not None, reject=None if args.reject is None else tuple(args.reject),
+                         unknowns=None if args.unknowns is None else [g for g in args.unknowns.split(",") if g])
     dst = args.out or os.path.join(args.map_dir, "MapObjects.reopt.txt")
     write_map_objects(dst, out)
     print("re-optimised %d of %d objects (%d with observations) on %d GPU(s) in %.3f s = %.1f objects/s -> %s" % (

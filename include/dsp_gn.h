@@ -639,7 +639,8 @@ int dsp_batch_enable_trace(dsp_batch* b, int on);
  * hash(ray << 6 | depth_index), hash(x) = (x * 2654435761) ^ (x >> 7), mod 2^32.  Any pointer may be NULL.
  * A pose-only batch (dsp_batch_create_pose) fills H as 6x6 (n_objects x 36), b and dx as 6 per object; its K is the number of points
  * the iteration's system was built from (M, or those the inlier filter kept after iteration 4), V = m = 0; of an iteration that finds
- * no point only K (= 0) is written. */
+ * no point only K (= 0) is written.  What an iteration does not write -- the rows of an object that has failed, or that the convergence
+ * rule has frozen -- reads as zeros. */
 int dsp_batch_trace(dsp_batch* b, int32_t iteration, float* H, float* bvec, float* dx, int64_t* V, int64_t* m,
                     int64_t* K, float* t_obj_cam, float* code, uint32_t* set_sums, float* depths /* 64 per object */);
 /* A multi-view batch (dsp_batch_create_multiview): dsp_batch_trace returns, per OBJECT, the pooled H, b, dx, the object's state, the

@@ -109,8 +109,9 @@ def _host_rays(rep, i, sdf_grid, depths, depth_fg, th):
     return fl, cn
 
 
-def _check_against_host(b, rep, rec, members, inputs, n_depth, th):
-    """Every evaluated member: the device's rays are the host function's, bit for bit."""
+def _check_against_host(b, rep, rec, members, inputs, n_depth, th, ray_w=None):
+    """Every evaluated member: the device's rays are the host function's, bit for bit.  ray_w (per member, optional): the observation
+    weights -- a ray of weight 0 is absent, its rows those of a member without a render term (NaN floats, zero counts)."""
     n = 0
     for i in members:
         rays, depth = inputs[i]
@@ -118,6 +119,8 @@ def _check_against_host(b, rep, rec, members, inputs, n_depth, th):
             continue
         _, sdf, _ = b.debug_samples(i, rays.shape[0], n_depth)
         fl, cn = _host_rays(rep, i, sdf, rec["depths"][i], depth, th)
+        if ray_w is not None:
+            fl[np.asarray(ray_w[i]) == 0], cn[np.asarray(ray_w[i]) == 0] = np.nan, 0
         for k, key in enumerate(("ray_depth", "ray_hit", "ray_residual")):
             assert _bits(_cut(rep, key, i), fl[:, k]), (i, key, np.abs(_cut(rep, key, i) - fl[:, k]).max())
         assert np.array_equal(_cut(rep, "ray_counts", i), cn), i

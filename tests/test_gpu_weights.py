@@ -126,9 +126,9 @@ def _without_rays(o, keep):
     return dict(o, rays=o["rays"][keep], depth=o["depth"][keep[:n_fg]])
 
 
-@pytest.mark.parametrize("n_depth", [50, 64])
-@pytest.mark.parametrize("which", ["one_latency_sized", "three_objects"])
-def test_zero_rays_equal_removal_bit_for_bit(eng, n_depth, which):
+def _zero_rays_equal_removal(eng, n_depth, which, configure=None):
+    """configure(b, objs): called on each of the two batches before it runs (tests/test_gpu_feature_forms.py pins a launch form there); what
+    it returns, if callable, is called on the batch after the run."""
     if which == "one_latency_sized":
         objs = [synth.make_object(720, n_surface=250, n_background=150, n_foreground=300)]
         assert objs[0]["rays"].shape[0] == 450
@@ -142,16 +142,27 @@ def test_zero_rays_equal_removal_bit_for_bit(eng, n_depth, which):
     n_it = 3
     prm = E.gn_params(num_iterations=n_it, num_depth_samples=n_depth)
     keys = ("H", "b", "dx", "V", "K", "m", "t_obj_cam", "code", "depths")       # (not set_sums: the checksums hash the ray's index)
-    b = _joint(eng, objs, prm)
-    b.set_observation_weights(None, [k.astype(F32) for k in keep])
-    weighted = _run(b, n_it, keys)
-    b.close()
-    b = _joint(eng, [_without_rays(o, k) for o, k in zip(objs, keep)], prm)
-    reduced = _run(b, n_it, keys)
-    b.close()
+    out = []
+    for weighted in (True, False):
+        objs_ = objs if weighted else [_without_rays(o, k) for o, k in zip(objs, keep)]
+        b = _joint(eng, objs_, prm)
+        after = configure(b, objs_) if configure is not None else None
+        if weighted:
+            b.set_observation_weights(None, [k.astype(F32) for k in keep])
+        out.append(_run(b, n_it, keys))
+        if callable(after):
+            after(b)
+        b.close()
+    weighted, reduced = out
     print("zero rays, D=%d, %s: status %s, V %s K %s at the last iteration" % (n_depth, which, weighted[3], weighted[-6], weighted[-5]))
     assert weighted[3].tolist() == [0] * len(objs) and all((weighted[4 + len(keys) * e + 4] > 0).all() for e in range(n_it))
     assert _same(weighted, reduced)
+
+
+@pytest.mark.parametrize("n_depth", [50, 64])
+@pytest.mark.parametrize("which", ["one_latency_sized", "three_objects"])
+def test_zero_rays_equal_removal_bit_for_bit(eng, n_depth, which):
+    _zero_rays_equal_removal(eng, n_depth, which)
 
 
 # ---- 3. weighted systems against fp64 --------------------------------------------------------------------------------------------------
@@ -169,21 +180,27 @@ def _metric_objects():
             synth.make_object(733, n_surface=2100, n_background=150, n_foreground=300)]
 
 
-def _check_joint_state(eng, dec, objs, prm, oprm, pw, rw, t, code, depths, want=None, label="", kind="joint"):
+def _check_joint_state(eng, dec, objs, prm, oprm, pw, rw, t, code, depths, want=None, label="", kind="joint", configure=None, check=None):
     """One iteration of a batch of `objs` with the weights (pw, rw per object; None = no weights) from the injected state, every object's
     system against the weighted fp64 reference on the device's own sets.  want: the (H, b, dx) bits the iteration must reproduce.
-    -> the iteration's trace."""
+    configure(b): called on the batch before it runs (tests/test_gpu_feature_forms.py pins a launch form there); what it returns, if
+    callable, is called on the batch after the run (the stats of the form that ran); check: the objects held to fp64 (None = all).  -> the iteration's trace."""
     n_d = oprm.num_depth_samples
     b = _joint(eng, objs, prm)
+    after = configure(b) if configure is not None else None
     if pw is not None or rw is not None:
         b.set_observation_weights(pw, rw)
     b.set_start_state(t, code, depths)
     b.set_iterations(1)
     b.run()
     tr = b.trace(0)
+    if callable(after):
+        after(b)
     if want is not None:
         assert all(np.array_equal(tr[k], want[k]) for k in ("H", "b", "dx", "V", "K")), "the re-run from the traced state does not reproduce the traced system"
     for i, o in enumerate(objs):
+        if check is not None and i not in check:
+            continue
         m, _, deds = b.debug_samples(i, o["rays"].shape[0], n_d)
         sets = W.device_sets(m, deds)
         assert sets["valid"][0].shape[0] == int(tr["V"][i]) and sets["kept"][0].shape[0] == int(tr["K"][i])
@@ -242,6 +259,35 @@ def test_weighted_pose_only_systems_against_fp64(eng, oracle_decoder):
         _note("pose_only", M.check_against_fp64(dev, lin, 0.0, what="weighted pose-only iteration %d" % e))
 
 
+def _check_multiview_states(b, dec, oprm, objs, pw, rw, traces, n_d, check=None, zero_views=(), label="weighted multi-view", kind="multiview"):
+    """Every traced iteration (trace, trace_views) of the weighted multi-view batch b run again from its traced state: the same bits, and the
+    pooled system of every object (check: of these objects) against the weighted fp64 reference on the device's own per-view sets."""
+    views = [v for o in objs for v in o["views"]]
+    off = np.concatenate([[0], np.cumsum([len(o["views"]) for o in objs])]).astype(int)
+    for e, (tr, tv) in enumerate(traces):
+        assert all(int(tv["V"][k]) == 0 and int(tv["K"][k]) == 0 for k in zero_views)
+        b.set_start_state(tr["t_obj_cam"], tr["code"], tv["depths"])
+        b.set_iterations(1)
+        b.run()
+        tr1, tv1 = b.trace(0), b.trace_views(0)
+        assert all(np.array_equal(tr1[k], tr[k]) for k in ("H", "b", "dx", "V", "K")) and np.array_equal(tv1["set_sums"], tv["set_sums"])
+        for i, o in enumerate(objs):
+            if check is not None and i not in check:
+                continue
+            rows = range(off[i], off[i + 1])
+            sets = []
+            for k in rows:
+                m, _, deds = b.debug_samples(k, views[k]["rays"].shape[0], n_d)
+                sets.append(W.device_sets(m, deds))
+            lin = W.linearise_multiview(dec, oprm, o["views"], tr["t_obj_cam"][i], tr["code"][i], [tv["depths"][k][:n_d] for k in rows], sets,
+                                        [pw[k] for k in rows], [rw[k] for k in rows])
+            assert lin["K_views"] == [int(tv["K"][k]) for k in rows] and int(tr["K"][i]) == sum(lin["K_views"])
+            dev = dict(H=tr["H"][i], b=tr["b"][i], dx=tr["dx"][i])
+            print("%s iteration %d object %d (%d views): K %s Mw %.6g Kw %.6g: %s" % (label, e, i, len(o["views"]), lin["K_views"], lin["Mw"], lin["Kw"],
+                                                                                      M.flat(M.scaled_errors(dev, lin, oprm.k4))))
+            _note(kind, M.check_against_fp64(dev, lin, oprm.k4, what="%s iteration %d object %d" % (label, e, i)))
+
+
 def test_weighted_ragged_multiview_systems_against_fp64(eng, oracle_decoder):
     case = X.case_ragged()
     objs = case["objects"]
@@ -252,34 +298,13 @@ def test_weighted_ragged_multiview_systems_against_fp64(eng, oracle_decoder):
     zero_view = 4                                            # the second of the last object's three views: all its weights 0
     pw[zero_view][:] = 0
     rw[zero_view][:] = 0
-    off = np.concatenate([[0], np.cumsum([len(o["views"]) for o in objs])]).astype(int)
     prm, oprm = E.gn_params(num_iterations=case["n_it"], **X.HYPER), X.oracle_params(case)
-    n_d = case["n_depth"]
     b = eng.multiview_batch(prm, [o["t"] for o in objs], [o["views"] for o in objs], trace=True)
     b.set_observation_weights(pw, rw)
     b.run()
     assert b.results()[3].tolist() == [0, 0, 0]
     traces = [(b.trace(e), b.trace_views(e)) for e in range(case["n_it"])]
-    for e, (tr, tv) in enumerate(traces):
-        assert int(tv["V"][zero_view]) == 0 and int(tv["K"][zero_view]) == 0
-        b.set_start_state(tr["t_obj_cam"], tr["code"], tv["depths"])
-        b.set_iterations(1)
-        b.run()
-        tr1, tv1 = b.trace(0), b.trace_views(0)
-        assert all(np.array_equal(tr1[k], tr[k]) for k in ("H", "b", "dx", "V", "K")) and np.array_equal(tv1["set_sums"], tv["set_sums"])
-        for i, o in enumerate(objs):
-            rows = range(off[i], off[i + 1])
-            sets = []
-            for k in rows:
-                m, _, deds = b.debug_samples(k, views[k]["rays"].shape[0], n_d)
-                sets.append(W.device_sets(m, deds))
-            lin = W.linearise_multiview(oracle_decoder, oprm, o["views"], tr["t_obj_cam"][i], tr["code"][i], [tv["depths"][k][:n_d] for k in rows], sets,
-                                        [pw[k] for k in rows], [rw[k] for k in rows])
-            assert lin["K_views"] == [int(tv["K"][k]) for k in rows] and int(tr["K"][i]) == sum(lin["K_views"])
-            dev = dict(H=tr["H"][i], b=tr["b"][i], dx=tr["dx"][i])
-            print("weighted multi-view iteration %d object %d (%d views): K %s Mw %.6g Kw %.6g: %s" % (e, i, len(o["views"]), lin["K_views"], lin["Mw"], lin["Kw"],
-                                                                                                    M.flat(M.scaled_errors(dev, lin, oprm.k4))))
-            _note("multiview", M.check_against_fp64(dev, lin, oprm.k4, what="weighted multi-view iteration %d object %d" % (e, i)))
+    _check_multiview_states(b, oracle_decoder, oprm, objs, pw, rw, traces, case["n_depth"], zero_views=(zero_view,))
     b.close()
 
 

@@ -145,6 +145,12 @@ SYMBOLS = [
     ("dsp_extract_meshes", C.c_int, [_VP, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, c_i64p, c_i64p]),
     ("dsp_meshes_fetch", C.c_int, [_VP, C.c_int64, c_i64p, c_i64p, c_f32p, c_i32p]),
     ("dsp_mesh_last_stats", C.c_int, [_VP, c_i64p, c_f32p]),
+    ("dsp_surface_points", C.c_int, [_VP, c_f32p, C.c_int64, c_i64p, c_f32p, C.c_int32, C.c_float, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_meshes_refine", C.c_int, [_VP, C.c_int64, c_i64p, C.c_int32, C.c_float, c_f64p]),
+    ("dsp_meshes_fetch_attributes", C.c_int, [_VP, C.c_int64, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_debug_surface_step", C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p]),
+    ("dsp_debug_surface_attributes", C.c_int, [C.c_int64, c_f32p, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_debug_surface_chunk_rows", C.c_int, [_VP, C.c_int64]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

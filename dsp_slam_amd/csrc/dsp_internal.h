@@ -511,4 +511,16 @@ hipError_t launch_mesh_band(const float* lp, const float4* grid, int n, int n_ob
                             long long* band_idx, int* cnt, int* tile0, int* n_tiles, int4* tiles, hipStream_t s);
 hipError_t launch_mesh_scatter(const float* band_val, const long long* band_idx, const int* cnt, int n, int n_obj, float* vol, hipStream_t s);
 
+// ---- surface projection (surface_kernels.hip; the arithmetic: surface_math.h) --------------------
+// pack: n packed float3 points -> the decoder's float4 list (unpack = 0) or the list -> out3 (unpack = 1).  step: point i moves by the tail
+// of row i.  attributes: one workgroup per tile {first point, count, object, row offset} of the decoder's list; var = [object][CODE_LEN]
+// floats or null (sigma is then not written); outputs indexed by point, any may be null.  A point that is not finite is NaN in every output.
+hipError_t launch_surface_pack(const float* p3, float4* p4, float* out3, int n, int unpack, hipStream_t s);
+hipError_t launch_surface_step(float4* pts, const float* rows, int n, float max_step, hipStream_t s);
+hipError_t launch_surface_attributes(const int4* tiles, int n_tiles, const float4* pts, const float* rows, const float* var, float* normals, float* grad_norm,
+                                     float* sdf, float* sigma, hipStream_t s);
+// surface_math.h compiled for the host in the translation unit that has contraction off (dsp_debug_surface_step / _attributes)
+void surface_step_host(int64_t n, const float* pts, const float* sdf, const float* grad_xyz, float max_step, float* pts_out);
+void surface_attributes_host(int64_t n, const float* rows68, const float* var64, float* normals, float* grad_norm, float* sdf, float* sigma);
+
 }  // namespace dsp

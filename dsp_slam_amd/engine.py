@@ -772,6 +772,85 @@ class Engine(object):
         ov, of = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(nf)])
         return [(verts[ov[i]:ov[i + 1]], faces[of[i]:of[i + 1]]) for i in range(n)]
 
+    # -- surface projection ------------------------------------------------------------------------
+    def _var_codes(self, var_code, n):
+        """(n, 64) float64 as the C ABI carries a code variance; shorter rows (a 32-D decoder's) are zero-padded."""
+        if var_code is None:
+            return None
+        v = np.asarray(var_code, np.float64).reshape(n, -1)
+        out = np.zeros((n, L.CODE_LEN), np.float64)
+        k = min(v.shape[1], L.CODE_LEN)
+        out[:, :k] = v[:, :k]
+        return out
+
+    def surface_points(self, codes, pts_list, steps=6, max_step=0.1, var_code=None):
+        """Projects object i's points pts_list[i] ((n_i, 3), object frame) onto the zero set of codes[i] with `steps` capped Newton steps
+        along the decoder's gradient (dsp_surface_points), all objects in one call.  A list of dicts with the keys of
+        extract_meshes_refined: `vertices` (the foot points), `faces` (empty: points have none), `normals` (unit, d sdf / d xyz at the
+        foot point), `sdf` there, `vertices_mc` (the points as given), and `grad_norm`, plus `sigma` (standard deviation of the surface
+        along the normal) when var_code ((n, code_len), e.g. a posterior's code variance) is given.  steps=0 evaluates at the points as
+        given.  max_step: the longest move of one step."""
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        n = codes.shape[0]
+        if n == 0:
+            return []
+        if len(pts_list) != n:
+            raise ValueError("one point array per code")
+        pts = [L.f32(p).reshape(-1, 3) for p in pts_list]
+        off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])]).astype(np.int64)
+        flat = L.f32(np.concatenate(pts, 0)) if off[-1] else np.zeros((0, 3), np.float32)
+        total = int(off[-1])
+        var = self._var_codes(var_code, n)
+        out_p, out_n = np.zeros((total, 3), np.float32), np.zeros((total, 3), np.float32)
+        sdf, gn = np.zeros(total, np.float32), np.zeros(total, np.float32)
+        sigma = np.zeros(total, np.float32) if var is not None else None
+        L.check(L.load().dsp_surface_points(self._h, L.ptr(codes), n, L.ptr(off, L.c_i64p), L.ptr(flat), int(steps), float(max_step),
+                                            L.ptr(var, L.c_f64p), L.ptr(out_p), L.ptr(out_n), L.ptr(sdf), L.ptr(gn), L.ptr(sigma)),
+                self._h, "dsp_surface_points")
+        res = []
+        for i in range(n):
+            s = slice(off[i], off[i + 1])
+            d = {"vertices": out_p[s], "faces": np.zeros((0, 3), np.int32), "normals": out_n[s], "sdf": sdf[s], "vertices_mc": flat[s],
+                 "grad_norm": gn[s]}
+            if sigma is not None:
+                d["sigma"] = sigma[s]
+            res.append(d)
+        return res
+
+    def extract_meshes_refined(self, codes, vol_dim, steps=6, regular_grid=False, prepass=None, delta=0.0, max_step=None, var_code=None):
+        """extract_meshes, then every vertex projected onto the decoder's zero set on the device (dsp_meshes_refine).  A list of dicts:
+        `vertices` (refined), `faces`, `normals` (analytic, unit), `sdf` (at the refined vertices), `vertices_mc` (the marching-cubes
+        vertices, what extract_meshes returns), plus `sigma` when var_code is given.  max_step None: one voxel per step."""
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        n = codes.shape[0]
+        if n == 0:
+            return []
+        nv, nf = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        lib = L.load()
+        L.check(lib.dsp_extract_meshes(self._h, L.ptr(codes), n, int(vol_dim), self._mesh_flags(regular_grid, prepass), float(delta),
+                                       L.ptr(nv, L.c_i64p), L.ptr(nf, L.c_i64p)), self._h, "dsp_extract_meshes")
+        tv = int(nv.sum())
+        verts_mc = np.zeros((tv, 3), np.float32)
+        faces = np.zeros((int(nf.sum()), 3), np.int32)
+        L.check(lib.dsp_meshes_fetch(self._h, n, L.ptr(nv, L.c_i64p), L.ptr(nf, L.c_i64p), L.ptr(verts_mc), L.ptr(faces, L.c_i32p)), self._h,
+                "dsp_meshes_fetch")
+        var = self._var_codes(var_code, n)
+        L.check(lib.dsp_meshes_refine(self._h, n, L.ptr(nv, L.c_i64p), int(steps), 0.0 if max_step is None else float(max_step),
+                                      L.ptr(var, L.c_f64p)), self._h, "dsp_meshes_refine")
+        verts, normals, sdf = np.zeros((tv, 3), np.float32), np.zeros((tv, 3), np.float32), np.zeros(tv, np.float32)
+        sigma = np.zeros(tv, np.float32) if var is not None else None
+        L.check(lib.dsp_meshes_fetch_attributes(self._h, n, L.ptr(nv, L.c_i64p), L.ptr(verts), L.ptr(normals), L.ptr(sdf), L.ptr(sigma)),
+                self._h, "dsp_meshes_fetch_attributes")
+        ov, of = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(nf)])
+        res = []
+        for i in range(n):
+            s = slice(ov[i], ov[i + 1])
+            d = {"vertices": verts[s], "faces": faces[of[i]:of[i + 1]], "normals": normals[s], "sdf": sdf[s], "vertices_mc": verts_mc[s]}
+            if sigma is not None:
+                d["sigma"] = sigma[s]
+            res.append(d)
+        return res
+
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
         c = np.zeros(5, np.int64)

@@ -379,3 +379,12 @@ class MeshExtractor(object):
         codes = [_f32(c)[:self.code_len] for c in codes]
         meshes = self.decoder.engine.extract_meshes(codes, self.voxels_dim, regular_grid=self.regular_grid, prepass=self.prepass)
         return [ForceKeyErrorDict(vertices=v, faces=f) for v, f in meshes]
+
+    def extract_refined_meshes_from_codes(self, codes, steps=6, var_codes=None):
+        """extract_meshes_from_codes with every vertex projected onto the decoder's zero set by `steps` capped Newton steps on the
+        device (dsp_meshes_refine): dicts with `vertices` (refined), `faces`, `normals` (the decoder's unit gradient), `sdf`,
+        `vertices_mc` (the marching-cubes vertices) and -- var_codes given, (n, code_len) code variances -- `sigma`.  (Addition.)"""
+        codes = [_f32(c)[:self.code_len] for c in codes]
+        meshes = self.decoder.engine.extract_meshes_refined(codes, self.voxels_dim, steps=steps, regular_grid=self.regular_grid,
+                                                            prepass=self.prepass, var_code=var_codes)
+        return [ForceKeyErrorDict(**m) for m in meshes]

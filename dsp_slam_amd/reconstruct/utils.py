@@ -167,3 +167,59 @@ def read_mesh_from_ply(ply_filename):
     if nf and not (faces["n"] == 3).all():
         raise ValueError("not a triangle mesh")
     return v, faces["vertex_indices"].astype(np.int32)
+
+
+def _ply_vertex_dtype(quality):
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    return np.dtype(fields + ([("quality", "<f4")] if quality else []))
+
+
+def write_mesh_to_ply_with_normals(v, n, f, ply_filename_out, quality=None):
+    """write_mesh_to_ply's file with per-vertex normals (nx, ny, nz float) and, quality given, one `quality` float per vertex (what
+    MeshLab and CloudCompare show as a scalar field).  (Addition; the reference writes no normals.)"""
+    v = np.asarray(v, "<f4").reshape(-1, 3)
+    n = np.asarray(n, "<f4").reshape(-1, 3)
+    f = np.asarray(f, "<i4").reshape(-1, 3)
+    if n.shape != v.shape or (quality is not None and np.asarray(quality).reshape(-1).shape[0] != v.shape[0]):
+        raise ValueError("one normal (and one quality value) per vertex")
+    verts = np.zeros(v.shape[0], _ply_vertex_dtype(quality is not None))
+    for k, name in enumerate(("x", "y", "z")):
+        verts[name] = v[:, k]
+        verts["n" + name] = n[:, k]
+    if quality is not None:
+        verts["quality"] = np.asarray(quality, "<f4").reshape(-1)
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+              + "".join("property float %s\n" % name for name in verts.dtype.names)
+              + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0])
+    faces = np.zeros(f.shape[0], dtype=[("n", "u1"), ("vertex_indices", "<i4", (3,))])
+    faces["n"] = 3
+    faces["vertex_indices"] = f
+    with open(ply_filename_out, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(verts.tobytes())
+        out.write(faces.tobytes())
+
+
+def read_mesh_from_ply_with_normals(ply_filename):
+    """Inverse of write_mesh_to_ply_with_normals: (vertices, normals, faces, quality or None)."""
+    with open(ply_filename, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    if head[0] != "ply" or head[1] != "format binary_little_endian 1.0":
+        raise ValueError("unsupported PLY flavour")
+    nv = int([h for h in head if h.startswith("element vertex")][0].split()[-1])
+    nf = int([h for h in head if h.startswith("element face")][0].split()[-1])
+    props = [h.split() for h in head if h.startswith("property float")]
+    names = [p[2] for p in props]
+    quality = names == list(_ply_vertex_dtype(True).names)
+    if not quality and names != list(_ply_vertex_dtype(False).names):
+        raise ValueError("not a PLY with normals in the layout of write_mesh_to_ply_with_normals")
+    dt = _ply_vertex_dtype(quality)
+    verts = np.frombuffer(data, dt, nv, end)
+    faces = np.frombuffer(data, np.dtype([("n", "u1"), ("vertex_indices", "<i4", (3,))]), nf, end + nv * dt.itemsize)
+    if nf and not (faces["n"] == 3).all():
+        raise ValueError("not a triangle mesh")
+    v = np.stack([verts["x"], verts["y"], verts["z"]], 1).astype(np.float32)
+    n = np.stack([verts["nx"], verts["ny"], verts["nz"]], 1).astype(np.float32)
+    return v, n, faces["vertex_indices"].astype(np.int32), (verts["quality"].astype(np.float32) if quality else None)

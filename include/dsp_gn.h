@@ -260,6 +260,41 @@ int dsp_marching_cubes(dsp_handle* h, const float* volume, int32_t n0, int32_t n
  * nothing is copied and DSP_E_STATE is returned. */
 int dsp_mesh_fetch(dsp_handle* h, float* vertices, int64_t n_vertices, int32_t* faces, int64_t n_faces);
 
+/* ---- surface projection: points onto the decoded zero set, with the decoder's own normals ------------------------------------------
+ * The decoder's forward + input-gradient launch (the one behind dsp_sdf_jacobian) gives sdf and g = d sdf / d xyz at a point; one step is
+ * p <- p - sdf g / |g|^2, capped at max_step in length (a longer step is scaled to max_step; a point whose |g|^2 is below 1e-20 or whose
+ * step is not finite stays where it is).  After n_steps steps one more launch gives, at the final points: normal = g / |g| (zero where
+ * |g|^2 < 1e-20), sdf, grad_norm = |g| and -- with a code variance -- sigma = sqrt(sum_k (d sdf / d code_k)^2 var_k) / |g|, the
+ * first-order standard deviation of the surface's displacement along the normal.  The arithmetic is csrc/surface_math.h, one correctly
+ * rounded fp32 operation at a time, the same on the device and in the dsp_debug_surface_* host functions.
+ *
+ * dsp_surface_points: n_codes objects (codes: n_codes x 64), object c owns pts[pts_off[c] .. pts_off[c+1]) (x 3 floats, object frame);
+ * pts_off has n_codes + 1 entries, non-decreasing from 0.  n_steps 0 .. 8 (0: attributes at the points as given).  max_step > 0.
+ * var_code: NULL or n_codes x 64 doubles as dsp_batch_posterior_fetch writes them (finite, >= 0, else DSP_E_ARG; entries at or beyond the
+ * decoder's code length are ignored).  Any output may be NULL; sigma requires var_code (DSP_E_ARG).  pts_out / normals: 3 floats per
+ * point; sdf / grad_norm / sigma: one.  Objects without points and a total of zero points are not errors.  A non-finite input point has
+ * NaN in its own outputs and disturbs no other point.  The work runs in chunks under a fixed device budget; a batched, ragged or
+ * chunked call computes each point exactly as a call with that point alone. */
+int dsp_surface_points(dsp_handle* h, const float* codes, int64_t n_codes, const int64_t* pts_off, const float* pts, int32_t n_steps, float max_step,
+                       const double* var_code, float* pts_out, float* normals, float* sdf, float* grad_norm, float* sigma);
+/* The same on the vertices of the last dsp_extract_meshes of this handle, device resident, with the codes that call was given (the handle
+ * keeps a host copy).  n_codes / n_vertices must be what that call returned (else DSP_E_STATE).  max_step <= 0: one voxel of that
+ * extraction, 2 / (vol_dim - 1).  The marching-cubes vertices stay what they are: dsp_meshes_fetch is unchanged.  The results stay on
+ * the device until the next dsp_extract_meshes on the handle. */
+int dsp_meshes_refine(dsp_handle* h, int64_t n_codes, const int64_t* n_vertices, int32_t n_steps, float max_step, const double* var_code);
+/* Copies what the last dsp_meshes_refine left, concatenated in object order like dsp_meshes_fetch: refined vertices and normals
+ * (sum n_vertices x 3), sdf and sigma (sum n_vertices); any may be NULL.  DSP_E_STATE: no refine since the last extraction, other
+ * counts, or sigma requested when the refine had no var_code. */
+int dsp_meshes_fetch_attributes(dsp_handle* h, int64_t n_codes, const int64_t* n_vertices, float* vertices, float* normals, float* sdf, float* sigma);
+/* Host only, no handle: csrc/surface_math.h's two functions on arrays.  dsp_debug_surface_step: n points, their sdf (n) and gradient
+ * (n x 3) -> pts_out (n x 3).  dsp_debug_surface_attributes: n rows of 68 floats {d sdf / d code [64], d sdf / d xyz [3], sdf} and ONE
+ * variance of 64 doubles (or NULL) for all of them; any output may be NULL, sigma requires var_code. */
+int dsp_debug_surface_step(int64_t n, const float* pts, const float* sdf, const float* grad_xyz, float max_step, float* pts_out);
+int dsp_debug_surface_attributes(int64_t n, const float* rows68, const double* var_code, float* normals, float* grad_norm, float* sdf, float* sigma);
+/* Testing: this handle's chunk budget of the surface projection in decoder rows (0 = the default, 64 MiB of rows), so that a small call
+ * crosses chunk borders. */
+int dsp_debug_surface_chunk_rows(dsp_handle* h, int64_t rows);
+
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,

@@ -18,6 +18,8 @@
 
 namespace dsp {
 
+constexpr int ZERO_VEC_BYTES = WIDTH * 4;     // behind the weight ring: see zero_l
+
 #define FOR16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 
 // MODE 0: forward only.  MODE 1: forward, relu masks kept and exported (with nothing else to do) for every sample whose
@@ -42,12 +44,16 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
     unsigned short* const mask_l = lds.mask;
     char* ring_ptr = smem + LDS_HEAD_BYTES + (MASKS ? MASK_BYTES : 0);
     const unsigned ring0 = lds_addr(ring_ptr);
+    // one all-zero 512-entry vector behind the ring: the "bias" of the passes that have none (pd.bias_row == -1), so that every
+    // group's accumulators are seeded by the same four LDS reads, without a branch in the MFMA stream
+    float* const zero_l = reinterpret_cast<float*>(ring_ptr + NBUF * CHUNK_BYTES);
 
     const int n_tiles = *a.n_tiles;
     const int tile0 = a.tile_begin ? *a.tile_begin : 0;
     if (tile0 + (int)blockIdx.x >= n_tiles) return;
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[0] = clock64(); a.clk[1] = wall_clock64(); }
-    stage_bias_table(a, bias_l, tid);
+    if (tid < ZERO_VEC_BYTES / 16) reinterpret_cast<float4*>(zero_l)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    stage_bias_table(a, bias_l, tid);     // (its barrier publishes the zero vector as well)
 
     // ---- weight stream state (all wave-uniform) ---------------------------------------------------
     int issue_pos = 0, issue_slot = 0, rd_slot = 0;
@@ -79,11 +85,14 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
     abuf[1] = *reinterpret_cast<const f32x4*>(ring_ptr + lane * 16 + 1024);
 
     float sin_[128];   // input slab of the current pass:  sin_[4t+r] = row 16t + 4g + r of point pl
-    f32x4 acc[32];     // output slab being produced: the MFMA accumulators of all 32 row tiles
+    f32x4 acc[2][4];   // MFMA accumulators of the output group being produced ([og & 1]) and of the one before / after it
+    f32x4 outv[32];    // output slab being produced: the finished groups' row tiles, outv[4 og + j][r] = row 64 og + 16 j + 4 g + r
 #pragma unroll
     for (int i = 0; i < 128; ++i) sin_[i] = 0.f;
 #pragma unroll
-    for (int i = 0; i < 32; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 32; ++i) outv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i >> 2][i & 3] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int tile = tile0 + blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int4 td = a.tiles[tile];
@@ -159,21 +168,35 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
             if (pd.kind == 2) reinject_xyz(sin_, g, a.lat_tile, pt);
             else if (BWD && pd.kind == 5) gfirst = first_layer_xyz_grad(a, bias_l, g, sin_);
 
-            // All 32 output tiles of the layer are MFMA accumulators (acc[4*og+j], 128 AGPRs) with static indices: the
-            // group / chunk / k-step loops are fully unrolled and skipped by uniform branches, so no register is ever
-            // indexed dynamically and the MFMA stream runs from one output group into the next without an epilogue.
+            // Output groups run one after the other on two ping-pong sets of four accumulator tiles (acc[og & 1][j], 32 AGPRs); a finished
+            // group's 64 rows wait in outv for the layer epilogue.  Group / chunk / k-step loops are fully unrolled and skipped by uniform
+            // branches, so no register is ever indexed dynamically.  The boundary og -> og + 1 holds the skip branches and the chunk's ring
+            // addresses, nothing that waits: no drain, no accumulator moves, no LDS round trip between the last MFMA of one group and the
+            // first of the next (profiles/group_boundaries.md has the generated sequence before and after, and what it was worth).
+            // Its work rides in group og + 1's chunk 0 (every pass has one), tile j of four per step:
+            //   * read-out of group og (accumulators -> outv): behind an MFMA of k-step 2 j + 1.  Only the pass's last group is read out
+            //     in the layer epilogue.
+            //   * seed of group og + 2 (its bias rows; the zero vector where the pass has no bias): read from LDS straight into the set
+            //     group og has just left, with the A operands of k-steps 2, 4, 6 and 12, whose wait two k-steps on covers it too.  It stays
+            //     the C operand of each tile's first MFMA.  A group past pd.nog is seeded as well: the reads stay inside the 512-entry
+            //     vector and the values are dropped.  Group 1 is seeded from group 0's chunk 0, group 0 ahead of the pass.
+            // pin_vgpr: empty asm that makes hipcc move the tile from accumulator to vector registers HERE, inside the k-step the
+            // sched_barriers fence; left alone it hoists the read-out to the group's last MFMA, where the matrix pipe has to drain first.
+            auto pin_vgpr = [](f32x4& t) __attribute__((always_inline)) { asm volatile("" : "=v"(t) : "0"(t)); };
+            const float* const seed_src = (pd.bias_row == -1 ? zero_l : pass_bias_vec(pd.bias_row, bias_l, cb_l)) + 4 * g;
+            auto seed_tile = [&](int og, int j) __attribute__((always_inline)) {       // seed of tile j of group og, into the group's set
+                acc[og & 1][j] = *reinterpret_cast<const f32x4*>(seed_src + 64 * og + 16 * j);
+            };
+            auto read_out = [&](int og, int j) __attribute__((always_inline)) {                 // tile j of finished group og: accumulators -> outv
+                f32x4 t = acc[og & 1][j];
+                pin_vgpr(t);
+                outv[4 * og + j] = t;
+            };
+#pragma unroll
+            for (int j = 0; j < 4; ++j) seed_tile(0, j);
 #pragma unroll
             for (int og = 0; og < 8; ++og) {
                 if (og < pd.nog) {
-                    f32x4 bias4[4];
-                    if (pd.bias_row != -1) {
-                        const float* bp = pass_bias_vec(pd.bias_row, bias_l, cb_l) + 64 * og + 4 * g;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bias4[j] = *reinterpret_cast<const f32x4*>(bp + 16 * j);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bias4[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    }
 #pragma unroll
                     for (int c = 0; c < 8; ++c) {
                         if (c < pd.nchunks) {
@@ -204,15 +227,23 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
                                 }
                                 const f32x4 av = abuf[s % (2 * PAIR_READS)];
                                 const float b = sin_[16 * c + s];
-                                acc[4 * og + 0] = MFMA16(av.x, b, (c == 0 && s == 0) ? bias4[0] : acc[4 * og + 0]);
+                                f32x4 (&ac)[4] = acc[og & 1];
+                                ac[0] = MFMA16(av.x, b, ac[0]);
                                 // refill of the slot freed by the barrier above: one DMA piece per k-step, behind an MFMA
                                 if (s == KSTEPS_PER_CHUNK / 2 + 0) { glds_set_dst(idst); glds_piece_m0<0>(isrc, lane_off, idst); };
                                 if (s == KSTEPS_PER_CHUNK / 2 + 1) glds_piece_m0<1>(isrc, lane_off, idst);
                                 if (s == KSTEPS_PER_CHUNK / 2 + 2) glds_piece_m0<2>(isrc, lane_off, idst);
                                 if (s == KSTEPS_PER_CHUNK / 2 + 3) { glds_piece_m0<3>(isrc, lane_off, idst); issue_next(); }
-                                acc[4 * og + 1] = MFMA16(av.y, b, (c == 0 && s == 0) ? bias4[1] : acc[4 * og + 1]);
-                                acc[4 * og + 2] = MFMA16(av.z, b, (c == 0 && s == 0) ? bias4[2] : acc[4 * og + 2]);
-                                acc[4 * og + 3] = MFMA16(av.w, b, (c == 0 && s == 0) ? bias4[3] : acc[4 * og + 3]);
+                                // the boundary work (above): read-out of the group before, then seed of the group after into the same set
+                                constexpr int SSTEP[4] = {2, 4, 6, 12};
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) {
+                                    if (og > 0 && c == 0 && s == 2 * j + 1) read_out(og - 1, j);
+                                    if (og < 7 && c == 0 && s == SSTEP[j]) seed_tile(og + 1, j);
+                                }
+                                ac[1] = MFMA16(av.y, b, ac[1]);
+                                ac[2] = MFMA16(av.z, b, ac[2]);
+                                ac[3] = MFMA16(av.w, b, ac[3]);
                                 // pin "read for k-step s+2, then the four MFMAs of k-step s": left alone, hipcc sinks
                                 // every ds_read next to its use (one A buffer, lgkmcnt(0) before each MFMA quad)
                                 __builtin_amdgcn_sched_barrier(0);
@@ -223,15 +254,19 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
                 }
             }
 
-            // ---- layer epilogue: relu (+ mask store) or mask apply, accumulators -> next layer's input slab ----------
+            // ---- layer epilogue: relu (+ mask store) or mask apply, finished rows -> next layer's input slab ------------------------
 #pragma unroll
             for (int og = 0; og < 8; ++og) {
                 if (og < pd.nog) {
+                    if (og == pd.nog - 1) {       // the last group has no successor to hide its read-out behind
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) read_out(og, j);
+                    }
                     float v[16];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        v[4 * j + 0] = acc[4 * og + j].x; v[4 * j + 1] = acc[4 * og + j].y;
-                        v[4 * j + 2] = acc[4 * og + j].z; v[4 * j + 3] = acc[4 * og + j].w;
+                        v[4 * j + 0] = outv[4 * og + j].x; v[4 * j + 1] = outv[4 * og + j].y;
+                        v[4 * j + 2] = outv[4 * og + j].z; v[4 * j + 3] = outv[4 * og + j].w;
                     }
                     if (pd.relu) {
                         if (MASKS) {
@@ -283,7 +318,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs a) {
 
 static void (*const MLP_KERNELS[4])(const MlpArgs) = {mlp_kernel<0>, mlp_kernel<1>, mlp_kernel<2>, mlp_kernel<3>};     // [MODE]
 
-size_t mlp_lds_bytes(int mode) { return LDS_HEAD_BYTES + (mode != 0 ? MASK_BYTES : 0) + NBUF * CHUNK_BYTES; }
+size_t mlp_lds_bytes(int mode) { return LDS_HEAD_BYTES + (mode != 0 ? MASK_BYTES : 0) + NBUF * CHUNK_BYTES + ZERO_VEC_BYTES; }
 
 // Opt every kernel variant into > 64 KiB of dynamic LDS on the current device (called by dsp_create).
 hipError_t mlp_prepare_device() {

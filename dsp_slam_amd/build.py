@@ -10,9 +10,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdspgn.so")
 SOURCES = ["mlp_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "gn_kernels.hip", "mesh_kernels.hip", "surface_kernels.hip", "dsp_gn.hip",
-           "pose_graph.cpp"]
+           "decoder_pack.hip", "decoder_pack_abi.hip", "pose_graph.cpp"]
 HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "surface_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(CSRC, "gn_solve_body.h"), os.path.join(CSRC, "gn_posterior_body.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
-           os.path.join(ROOT, "include", "dsp_pose_graph.h")]
+           os.path.join(CSRC, "batch_tokens.h"), os.path.join(CSRC, "decoder_pack.h"), os.path.join(CSRC, "host_common.h"), os.path.join(ROOT, "include", "dsp_pose_graph.h")]
 
 
 def _hipcc():
@@ -148,7 +148,7 @@ def build(force=False, verbose=False):
         with open(info, "w") as f:
             f.write(text)
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as ex:
         objs = list(ex.map(lambda s: _compile_one(hipcc, s, verbose), SOURCES))
     if os.environ.get("DSP_SKIP_ISA_CHECK") != "1":
         check_isa(verbose)          # before linking: a library that violates the assumptions is never produced

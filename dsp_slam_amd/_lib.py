@@ -21,6 +21,7 @@ GRAD_DIM = 67
 OBJ_GOOD, OBJ_FEW_SAMPLES, OBJ_NAN = 0, 1, 2
 PREPASS_OFF, PREPASS_F16, PREPASS_BF16 = 0, 1, 2
 MESH_REGULAR_GRID, MESH_PREPASS_F16, MESH_PREPASS_BF16 = 1, 2, 4     # dsp_extract_mesh(es) flags
+QUERY_NORMALS = 1                                                    # dsp_map_query flags
 PREPASS_SMALL_TILES = 0x100
 COMPUTE_F32, COMPUTE_F16, COMPUTE_BF16 = 0, 1, 2
 POSTERIOR_MEAN, POSTERIOR_SUM = 0, 1                       # dsp_batch_posterior: weights
@@ -151,6 +152,13 @@ SYMBOLS = [
     ("dsp_debug_surface_step", C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p]),
     ("dsp_debug_surface_attributes", C.c_int, [C.c_int64, c_f32p, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p]),
     ("dsp_debug_surface_chunk_rows", C.c_int, [_VP, C.c_int64]),
+    ("dsp_map_query", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, c_i32p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_map_query_last_stats", C.c_int, [_VP, c_i64p]),
+    ("dsp_debug_query_invert", C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p]),
+    ("dsp_debug_query_candidates", C.c_int, [C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.POINTER(C.c_uint8), c_f32p]),
+    ("dsp_debug_query_select", C.c_int, [C.c_int64, c_f32p, c_f32p, c_i32p, c_i32p, C.c_int64, c_i32p, c_f32p]),
+    ("dsp_debug_query_chunk_rows", C.c_int, [_VP, C.c_int64]),
+    ("dsp_debug_query_timing", C.c_int, [_VP, C.c_int, c_f64p]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

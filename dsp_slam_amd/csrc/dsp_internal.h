@@ -523,4 +523,28 @@ hipError_t launch_surface_attributes(const int4* tiles, int n_tiles, const float
 void surface_step_host(int64_t n, const float* pts, const float* sdf, const float* grad_xyz, float max_step, float* pts_out);
 void surface_attributes_host(int64_t n, const float* rows68, const float* var64, float* normals, float* grad_norm, float* sdf, float* sigma);
 
+// ---- map query (query_kernels.hip; the arithmetic: query_math.h) ---------------------------------
+// tab: the objects of the call, query_math::OBJ_STRIDE floats each {[R_ow | t_ow] 12, s, s_sel, 0, 0}: s scales the sphere bound, s_sel the
+// decoder's sdf (NaN for an object that must never win).  A pass = points [p0, p0 + n) of pts3 (packed float3, world frame), n_waves = ceil(n / 64).
+// count: wave_cnt[n_obj][n_waves] <- contained points per (object, wave), then its exclusive scan over the waves in place and cnt[obj] = the
+//   object's candidates; bound[p0 + i] and best[p0 + i] (the all-ones key) for every point of the pass.
+// fill: for the chunk's objects [o0, o0 + nc), candidate j of object o0 + k gets chunk row base[k] + j; rows inside [0, n_rows) are written:
+//   p_o to pts4 (the decoder's list), {point, object} to row_meta.
+// reduce: best[point] = min(., key) over the chunk's rows, sdf from out[row] (forward form) or out[row][67] (jacobian_rows); with normal != null
+//   the row that holds its point's best key then writes its world normal.
+// finish: best -> obj, dist; normal (optional) zeroed where there is no winner.
+hipError_t launch_query_count(const float* pts3, int64_t p0, int n, const float* tab, int n_obj, int n_waves, int* wave_cnt, int* cnt, float* bound,
+                              unsigned long long* best, hipStream_t s);
+hipError_t launch_query_fill(const float* pts3, int64_t p0, int n, const float* tab, int o0, int nc, const int* base, int n_waves, const int* wave_base,
+                             int n_rows, float4* pts4, int2* row_meta, hipStream_t s);
+hipError_t launch_query_reduce(const float* out, bool jacobian_rows, const int2* row_meta, int n_rows, const float* tab, int n_obj, int64_t n_pts,
+                               unsigned long long* best, float* normal, hipStream_t s);
+hipError_t launch_query_finish(const unsigned long long* best, int64_t n, int* obj, float* dist, float* normal, hipStream_t s);
+// query_math.h compiled for the host in the translation unit that has contraction off (dsp_map_query's pose inversion, dsp_debug_query_*)
+bool query_invert_host(const float* t16, float* rt12, float* scale);
+void query_candidates_host(int64_t n_obj, const float* rt, const float* scale, int64_t n_pts, const float* pts, float* p_obj, unsigned char* inside,
+                           float* bound);
+void query_select_host(int64_t n_rows, const float* sdf, const float* scale_of_row, const int32_t* obj_of_row, const int32_t* pt_of_row, int64_t n_pts,
+                       int32_t* obj, float* dist);
+
 }  // namespace dsp

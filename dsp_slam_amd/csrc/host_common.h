@@ -249,6 +249,15 @@ struct dsp_handle {
     // surface projection (surface_run): per-object variances of a call, and the chunk budget in rows (0 = SURFACE_CHUNK_BYTES; dsp_debug_surface_chunk_rows)
     DevBuf<float> sf_var;
     int64_t sf_chunk_rows = 0;
+    // map query (query_run): a pass's wave counts and object counts; a chunk's row bases and row -> {point, object}; the chunk budget in
+    // rows (0 = QUERY_CHUNK_BYTES; dsp_debug_query_chunk_rows) and the last call's stats.  (The call's own arrays -- points, object table,
+    // per-point results -- are blocks of the pool for the length of the call.)
+    DevBuf<int> q_wave_cnt, q_cnt, q_base;
+    DevBuf<int2> q_row_meta;
+    int64_t q_chunk_rows = 0;
+    int64_t q_stats[4] = {0, 0, 0, 0};      // candidate rows, decoder tiles, chunks, point passes
+    bool q_timing = false;                  // dsp_debug_query_timing: bracket the decoder launches with events ...
+    double q_ms[2] = {0.0, 0.0};            // ... {decoder launches, whole call} of the last call, ms on the handle's stream
     // dsp_mesh_last_stats: prepass points, fp32 band points, fp32 audit points, points decoded densely in fp32, objects re-run dense;
     // largest guard error
     int64_t ms_counts[5] = {0, 0, 0, 0, 0};

@@ -851,6 +851,34 @@ class Engine(object):
             res.append(d)
         return res
 
+    # -- map query ---------------------------------------------------------------------------------
+    def query_map(self, t_world_obj, codes, pts_world, normals=False):
+        """Signed distance of world points to a map of posed objects (dsp_map_query).  t_world_obj: (n_obj, 4, 4) object-to-world Sim(3);
+        codes: n_obj codes; pts_world: (n_pts, 3).  A dict: `obj` (int32, index of the object with the smallest world-scaled signed distance
+        among those whose unit sphere contains the point, -1 for none), `dist` (sdf * scale of that object, +inf for none), `bound`
+        (distance to the nearest unit sphere the point is outside of: dist <= bound certifies obj) and, with normals=True, `normal`
+        ((n_pts, 3), the winning surface's unit outward normal in the world frame, zeros for none)."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        pts = L.f32(np.asarray(pts_world, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        out = {"obj": np.zeros(n, np.int32), "dist": np.zeros(n, np.float32), "bound": np.zeros(n, np.float32)}
+        if normals:
+            out["normal"] = np.zeros((n, 3), np.float32)
+        L.check(L.load().dsp_map_query(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), n, L.QUERY_NORMALS if normals else 0,
+                                       L.ptr(out["obj"], L.c_i32p), L.ptr(out["dist"]), L.ptr(out["bound"]), L.ptr(out.get("normal"))),
+                self._h, "dsp_map_query")
+        return out
+
+    def query_stats(self):
+        """Counts of the last query_map on this engine (dsp_map_query_last_stats)."""
+        c = np.zeros(4, np.int64)
+        L.check(L.load().dsp_map_query_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_query_last_stats")
+        return {"rows": int(c[0]), "tiles": int(c[1]), "chunks": int(c[2]), "passes": int(c[3])}
+
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
         c = np.zeros(5, np.int64)

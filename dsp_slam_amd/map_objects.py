@@ -42,3 +42,30 @@ def write_map_objects(path, objects):
             items = ["%.9f" % float(v) for v in np.asarray(o["code"], np.float32).reshape(-1)]
             width = max(len(x) for x in items) if items else 0
             f.write(" ".join(x.rjust(width) for x in items) + "\n")
+
+
+def query_points(engine, objects, pts_world, normals=False):
+    """Engine.query_map on the list read_map_objects returns: which object of the map every world point belongs to, its signed distance to that
+    object's surface (world units) and -- normals=True -- the surface's outward normal there.  The result dict of Engine.query_map (obj, dist,
+    bound, normal) plus `id`: the map's object id per point, -1 where obj is -1."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    res = engine.query_map(poses, [o["code"] for o in objects], pts_world, normals=normals)
+    return with_ids(res, [o["id"] for o in objects])
+
+
+def with_ids(result, ids):
+    """result (an Engine.query_map dict) with `id` added: ids[obj] per point, -1 where obj is -1."""
+    out = dict(result)
+    obj = np.asarray(result["obj"], np.int64)
+    table = np.asarray(list(ids) + [-1], np.int64)          # obj == -1 reads the last entry
+    out["id"] = table[obj]
+    return out
+
+
+def associate(result, max_dist):
+    """Per object id of a query_points result, the indices (ascending) of the points it won with dist <= max_dist: {id: int64 array}.  Objects
+    that won no such point are absent."""
+    ids = np.asarray(result["id"], np.int64)
+    keep = np.flatnonzero((np.asarray(result["obj"]) >= 0) & (np.asarray(result["dist"]) <= max_dist))
+    return {int(i): keep[ids[keep] == i] for i in np.unique(ids[keep])}

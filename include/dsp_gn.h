@@ -295,6 +295,54 @@ int dsp_debug_surface_attributes(int64_t n, const float* rows68, const double* v
  * crosses chunk borders. */
 int dsp_debug_surface_chunk_rows(dsp_handle* h, int64_t rows);
 
+/* ---- map query: signed distance and normal of world points to a map of posed objects ------------------------------------------------
+ * A map is n_obj objects, each an object-to-world Sim(3) pose (4x4 row-major, as MapObjects.txt carries it) and a code.  For every world
+ * point the call answers: which object, how far from its surface, and -- with DSP_QUERY_NORMALS -- in which direction the surface lies.
+ *   obj    index of the object with the smallest world-scaled signed distance among the objects whose unit sphere (object frame) contains
+ *          the point; -1 if no sphere contains it.  Equal distances go to the lower index.
+ *   dist   that object's sdf * s, s its object-to-world scale: negative inside the shape; +inf when obj == -1.
+ *   bound  the minimum over the objects whose sphere does NOT contain the point of (|p_o| - 1) * s, the distance to that sphere; +inf if
+ *          there is none.  The decoder says nothing beyond its sphere, so dist <= bound certifies that obj really is the nearest object,
+ *          and min(dist, bound) is the clearance a planner would use.
+ *   normal the unit outward normal of the winning object's surface in the WORLD frame: the decoder's own d sdf / d xyz, rotated and
+ *          normalised; zeros when obj == -1 or when |g|^2 < 1e-20 (the rule of dsp_surface_points).
+ * DeepSDF's output is a clamped (tanh) distance: metric near the surface, saturating away from it.  So dist is exact in sign, exact near
+ * the surface, and an under-estimate in magnitude far from it.
+ * A point with a NaN coordinate is inside nothing: obj -1, dist +inf, bound NaN; it disturbs no other point.  An object whose decoded
+ * distance is NaN, or whose code is not finite, never wins (its sphere still counts in bound).  The arithmetic is csrc/query_math.h, one
+ * correctly rounded fp32 operation at a time (the pose inversion: fp64 on the host, rounded once); the decoder rows are those of
+ * dsp_decode_sdf / dsp_sdf_jacobian at the object-frame points, bit for bit, and the result does not depend on chunking or on the order
+ * in which rows are reduced: two calls return the same bytes.
+ *
+ * dsp_map_query: t_world_obj n_obj x 16, codes n_obj x 64 (a 32-D decoder reads the first 32 of each row), pts_world n_pts x 3.  flags: 0
+ * or DSP_QUERY_NORMALS; normal (n_pts x 3) is required with the flag and must be NULL without it.  n_obj == 0 is valid (-1, +inf, +inf
+ * for every point), so is n_pts == 0.  DSP_E_ARG: a NULL output other than normal, a negative count, an unknown flag, or a pose that is
+ * not finite, has a bottom row other than 0 0 0 1, has no positive scale, or whose linear part over its scale is not a rotation (R^T R
+ * off the identity by more than 1e-4, the test of dsp_reconstruct_multiview's view transforms).  The work runs in passes of at most
+ * 131 072 points and chunks of at most 64 MiB of decoder rows, both fixed, whatever the device has free. */
+#define DSP_QUERY_NORMALS 1   /* flags: also return the winning object's world-frame unit normal (the decoder's forward + gradient form) */
+int dsp_map_query(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, int64_t n_pts, int32_t flags,
+                  int32_t* obj, float* dist, float* bound, float* normal);
+/* Counts of the last dsp_map_query on this handle: counts4 = {candidate rows (point-in-sphere pairs, each decoded once), decoder tiles of
+ * up to 64 rows, chunks, point passes}. */
+int dsp_map_query_last_stats(dsp_handle* h, int64_t* counts4);
+/* Host only, no handle: csrc/query_math.h on arrays.  dsp_debug_query_invert: n_obj poses -> rt_ow (n_obj x 12: [R_ow | t_ow], row-major
+ * 3 x 4) and scale (n_obj); DSP_E_ARG for a pose dsp_map_query refuses.  dsp_debug_query_candidates: p_obj (n_obj x n_pts x 3, object
+ * major), inside (n_obj x n_pts bytes) and bound (n_pts); any output may be NULL.  dsp_debug_query_select: n_rows decoder values with
+ * their object's scale, object index and point index -> obj / dist per point, the selection of dsp_map_query. */
+int dsp_debug_query_invert(int64_t n_obj, const float* t_world_obj, float* rt_ow, float* scale);
+int dsp_debug_query_candidates(int64_t n_obj, const float* rt_ow, const float* scale, int64_t n_pts, const float* pts_world, float* p_obj,
+                               unsigned char* inside, float* bound);
+int dsp_debug_query_select(int64_t n_rows, const float* sdf, const float* scale_of_row, const int32_t* obj_of_row, const int32_t* pt_of_row,
+                           int64_t n_pts, int32_t* obj, float* dist);
+/* Testing: this handle's chunk budget of the map query in decoder rows (0 = the default, 64 MiB of rows), so that a small call crosses
+ * chunk borders. */
+int dsp_debug_query_chunk_rows(dsp_handle* h, int64_t rows);
+/* Measurement: on != 0 brackets the following dsp_map_query calls on this handle, and every decoder launch inside them, with HIP events on
+ * the handle's stream; ms2 (optional) receives {decoder launches, whole call} of the last such call in milliseconds (0, 0 before one).
+ * The results of a call do not depend on it. */
+int dsp_debug_query_timing(dsp_handle* h, int on, double* ms2);
+
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,

@@ -22,6 +22,8 @@ OBJ_GOOD, OBJ_FEW_SAMPLES, OBJ_NAN = 0, 1, 2
 PREPASS_OFF, PREPASS_F16, PREPASS_BF16 = 0, 1, 2
 MESH_REGULAR_GRID, MESH_PREPASS_F16, MESH_PREPASS_BF16 = 1, 2, 4     # dsp_extract_mesh(es) flags
 QUERY_NORMALS = 1                                                    # dsp_map_query flags
+ALIGN_OK, ALIGN_CONVERGED, ALIGN_NO_SUPPORT, ALIGN_SINGULAR = 0, 1, 2, 3      # dsp_map_align: a hypothesis' status
+ALIGN_RECORD, ALIGN_TRACE = 50, 53                                   # ... doubles per record / per traced evaluation
 PREPASS_SMALL_TILES = 0x100
 COMPUTE_F32, COMPUTE_F16, COMPUTE_BF16 = 0, 1, 2
 POSTERIOR_MEAN, POSTERIOR_SUM = 0, 1                       # dsp_batch_posterior: weights
@@ -43,6 +45,12 @@ class GnParams(C.Structure):
                 ("b1", C.c_float), ("b2", C.c_float), ("lr", C.c_float), ("s_damp", C.c_float),
                 ("num_iterations", C.c_int32), ("num_depth_samples", C.c_int32), ("cut_off", C.c_float),
                 ("pose_only_iterations", C.c_int32)]
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("min_points", C.c_int32), ("max_dist", C.c_double), ("huber", C.c_double), ("damp", C.c_double),
+                ("trans_tol", C.c_double), ("rot_tol", C.c_double),
+                ("lambda0", C.c_double), ("up", C.c_double), ("down", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
 
 
 class Stats(C.Structure):
@@ -159,6 +167,13 @@ SYMBOLS = [
     ("dsp_debug_query_select", C.c_int, [C.c_int64, c_f32p, c_f32p, c_i32p, c_i32p, C.c_int64, c_i32p, c_f32p]),
     ("dsp_debug_query_chunk_rows", C.c_int, [_VP, C.c_int64]),
     ("dsp_debug_query_timing", C.c_int, [_VP, C.c_int, c_f64p]),
+    ("dsp_align_params_default", None, [C.POINTER(AlignParams)]),
+    ("dsp_map_align", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f64p, C.c_int64, C.POINTER(AlignParams), c_f64p, c_f64p,
+                                c_i32p, c_f32p, c_f64p]),
+    ("dsp_map_align_last_stats", C.c_int, [_VP, c_i64p]),
+    ("dsp_debug_align_check", C.c_int, [C.POINTER(AlignParams), c_f64p, C.c_int64, c_f32p, C.c_int64]),
+    ("dsp_debug_align_rows", C.c_int, [C.c_int64, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_double, C.c_double, c_f64p]),
+    ("dsp_debug_align_step", C.c_int, [c_f64p, c_f64p, C.c_double, C.c_double, c_f64p, c_i32p, c_f64p, c_f64p]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

@@ -9,9 +9,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdspgn.so")
-SOURCES = ["mlp_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "gn_kernels.hip", "mesh_kernels.hip", "surface_kernels.hip", "query_kernels.hip", "dsp_gn.hip",
+SOURCES = ["mlp_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "gn_kernels.hip", "mesh_kernels.hip", "surface_kernels.hip", "query_kernels.hip", "align_kernels.hip", "dsp_gn.hip",
            "decoder_pack.hip", "decoder_pack_abi.hip", "pose_graph.cpp"]
-HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "surface_math.h"), os.path.join(CSRC, "query_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(CSRC, "gn_solve_body.h"), os.path.join(CSRC, "gn_posterior_body.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
+HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "surface_math.h"), os.path.join(CSRC, "query_math.h"), os.path.join(CSRC, "align_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(CSRC, "gn_solve_body.h"), os.path.join(CSRC, "gn_posterior_body.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
            os.path.join(CSRC, "batch_tokens.h"), os.path.join(CSRC, "decoder_pack.h"), os.path.join(CSRC, "host_common.h"), os.path.join(ROOT, "include", "dsp_pose_graph.h")]
 
 
@@ -35,7 +35,7 @@ def is_stale():
 # spellings do not prevent that on their own (they are plain `*`/`+` in clang's HIP headers), so these files are compiled with
 # contraction off; explicit fmaf() calls stay FMAs.  mlp_kernel.hip keeps the default (its MFMA / fmaf use is explicit anyway).
 EXTRA_FLAGS = {"gn_kernels.hip": ["-ffp-contract=off"], "mesh_kernels.hip": ["-ffp-contract=off"],
-               "surface_kernels.hip": ["-ffp-contract=off"], "query_kernels.hip": ["-ffp-contract=off"], "pose_graph.cpp": ["-ffp-contract=off"]}
+               "surface_kernels.hip": ["-ffp-contract=off"], "query_kernels.hip": ["-ffp-contract=off"], "align_kernels.hip": ["-ffp-contract=off"], "pose_graph.cpp": ["-ffp-contract=off"]}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 
@@ -67,10 +67,10 @@ def _compile_one(hipcc, src, verbose):
 OBJDUMP_CANDIDATES = ("/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/llvm/bin/llvm-objdump")
 READELF_CANDIDATES = ("/opt/rocm/lib/llvm/bin/llvm-readelf", "/opt/rocm/llvm/bin/llvm-readelf")
 NO_SCRATCH_KERNELS = ("mlp_kernelILi0", "mlp_kernelILi1", "mlp_kernelILi2", "mlp_kernelILi3", "mlp_split_kernel", "mlp_cluster_kernel", "mlp_lp_kernelILb0",
-                      "mlp_lpj_fwd_kernel", "mlp_lpj_bwd_kernel", "k_query_")
+                      "mlp_lpj_fwd_kernel", "mlp_lpj_bwd_kernel", "k_query_", "k_align_")
 DECODER_SOURCES = ("mlp_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip")
 # bandwidth-bound kernels that are only held to "no scratch": their register and scratch figures join the report, the M0 / LDS-DMA rules do not apply
-PLAIN_SOURCES = ("query_kernels.hip",)
+PLAIN_SOURCES = ("query_kernels.hip", "align_kernels.hip")
 
 
 class IsaCheckError(RuntimeError):

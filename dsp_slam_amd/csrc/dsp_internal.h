@@ -547,4 +547,24 @@ void query_candidates_host(int64_t n_obj, const float* rt, const float* scale, i
 void query_select_host(int64_t n_rows, const float* sdf, const float* scale_of_row, const int32_t* obj_of_row, const int32_t* pt_of_row, int64_t n_pts,
                        int32_t* obj, float* dist);
 
+// ---- map alignment (align_kernels.hip; the arithmetic: align_math.h) ----------------------------
+// hyp: ALIGN_HYP_STRIDE floats per hypothesis {[R | t] of the sensor-to-world pose in fp32, 12; live (1 / 0); 0, 0, 0}.  Rows are
+// r = h n_pts + i.  transform: rows [r0, r0 + n) of pts_w <- to_object(rt_h, pts_s[i]), NaN for an ended hypothesis.  winner: behind a
+// chunk's launch_query_reduce (jacobian rows), the row that holds its point's best key writes the world gradient of d.  gram: the
+// align_math::NSUM sums of every live hypothesis through the written tree: slab[n_hyp][align_gram_blocks(n_pts)][NSUM] -> sums[n_hyp][NSUM].
+constexpr int ALIGN_HYP_STRIDE = 16;
+hipError_t launch_align_transform(const float* pts_s, int64_t n_pts, const float* hyp, int64_t r0, int64_t n, float* pts_w, hipStream_t s);
+hipError_t launch_align_winner(const float* rows, const int2* row_meta, int n_rows, const float* tab, int n_obj, int64_t n_pts,
+                               const unsigned long long* best, float* grad_w, hipStream_t s);
+hipError_t launch_align_gram(const float* pts_w, const int* obj, const float* dist, const float* grad_w, const float* weights, int64_t n_pts, int n_hyp,
+                             const float* hyp, double huber, double max_dist, double* slab, double* sums, hipStream_t s);
+int64_t align_gram_blocks(int64_t n_pts);
+// align_math.h compiled for the host in the translation unit that has contraction off (dsp_map_align's step, dsp_debug_align_*)
+bool align_check_pose_host(const double* t16, float* rt12);
+void align_rows_host(int64_t n, const float* pts_w, const int32_t* obj, const float* dist, const float* grad_w, const float* weights, double huber,
+                     double max_dist, double* sums);
+double align_cost_host(const double* sums, double huber, double max_dist);
+bool align_solve_host(const double* H36, const double* b6, double damp, double lambda, double* xi6);
+void align_apply_step_host(const double* xi6, const double* t_in, double* t_out);
+
 }  // namespace dsp

@@ -258,6 +258,8 @@ struct dsp_handle {
     int64_t q_stats[4] = {0, 0, 0, 0};      // candidate rows, decoder tiles, chunks, point passes
     bool q_timing = false;                  // dsp_debug_query_timing: bracket the decoder launches with events ...
     double q_ms[2] = {0.0, 0.0};            // ... {decoder launches, whole call} of the last call, ms on the handle's stream
+    // map alignment (align_run) runs the query's core on the scratch above; the last call's stats
+    int64_t a_stats[5] = {0, 0, 0, 0, 0};   // candidate rows, decoder tiles, chunks, point passes, evaluations
     // dsp_mesh_last_stats: prepass points, fp32 band points, fp32 audit points, points decoded densely in fp32, objects re-run dense;
     // largest guard error
     int64_t ms_counts[5] = {0, 0, 0, 0, 0};

@@ -879,6 +879,78 @@ class Engine(object):
         L.check(L.load().dsp_map_query_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_query_last_stats")
         return {"rows": int(c[0]), "tiles": int(c[1]), "chunks": int(c[2]), "passes": int(c[3])}
 
+    # -- map alignment -----------------------------------------------------------------------------
+    @staticmethod
+    def align_params(**params):
+        """dsp_align_params: the library's defaults with `params` written over them.  Fields: iterations, min_points, max_dist, huber, damp,
+        trans_tol, rot_tol, and step_control=(lambda0, up, down, lambda_min, lambda_max) (or the five by name)."""
+        prm = L.AlignParams()
+        L.load().dsp_align_params_default(C.byref(prm))
+        sc = params.pop("step_control", None)
+        if sc is not None:
+            prm.lambda0, prm.up, prm.down, prm.lambda_min, prm.lambda_max = [float(x) for x in sc]
+        names = {n for n, _ in L.AlignParams._fields_}
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("align_to_map: unknown parameter %r" % k)
+            setattr(prm, k, int(v) if k in ("iterations", "min_points") else float(v))
+        return prm
+
+    def align_to_map(self, t_world_obj, codes, pts_sensor, t_world_sensor0, weights=None, trace=False, per_point=False, **params):
+        """Where is the sensor?  Batched SE(3) Gauss-Newton of sensor-frame points against the map's decoded surfaces (dsp_map_align), one run
+        per initial pose of t_world_sensor0 ((n_hyp, 4, 4) or (4, 4), sensor-to-world, rigid), all on the device in one call.  The map as
+        query_map takes it; weights: None or (n_pts,) >= 0; params: see align_params.  A dict: `pose` (n_hyp, 4, 4) float64, `status`
+        (L.ALIGN_*), `cost`, `cost0` (truncated Huber cost at the returned / the first state), `n_used`, `sum_w`, `evaluations`, `steps`,
+        `lambda`, `information` (n_hyp, 6, 6: H of xi = [v, omega] at the returned state, undamped), `b` (n_hyp, 6), `best` (index of the
+        lowest cost among the hypotheses with support, -1 if none has any); with per_point=True `obj` / `dist` (n_hyp, n_pts) at the returned
+        state; with trace=True `trace`: a dict of per-evaluation arrays (n_hyp, iterations, ...): pose, decision, cost, lambda, n_used,
+        H (6, 6), b, xi."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        pts = L.f32(np.asarray(pts_sensor, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        w = None
+        if weights is not None:
+            w = L.f32(np.asarray(weights, np.float32).reshape(-1))
+            if w.shape[0] != n:
+                raise ValueError("one weight per point")
+        t0 = np.ascontiguousarray(np.asarray(t_world_sensor0, np.float64).reshape(-1, 4, 4))
+        n_hyp = t0.shape[0]
+        prm = self.align_params(**params)
+        iters = max(int(prm.iterations), 0)
+        pose, rec = np.zeros((n_hyp, 4, 4), np.float64), np.zeros((n_hyp, L.ALIGN_RECORD), np.float64)
+        obj = np.zeros((n_hyp, n), np.int32) if per_point else None
+        dist = np.zeros((n_hyp, n), np.float32) if per_point else None
+        tr = np.zeros((n_hyp, iters, L.ALIGN_TRACE), np.float64) if trace else None
+        L.check(L.load().dsp_map_align(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), L.ptr(w), n, L.ptr(t0, L.c_f64p), n_hyp, C.byref(prm),
+                                       L.ptr(pose, L.c_f64p), L.ptr(rec, L.c_f64p), L.ptr(obj, L.c_i32p), L.ptr(dist), L.ptr(tr, L.c_f64p)),
+                self._h, "dsp_map_align")
+        out = {"pose": pose, "status": rec[:, 0].astype(np.int32), "evaluations": rec[:, 1].astype(np.int32), "steps": rec[:, 2].astype(np.int32),
+               "cost0": rec[:, 3].copy(), "cost": rec[:, 4].copy(), "n_used": rec[:, 5].astype(np.int64), "sum_w": rec[:, 6].copy(),
+               "lambda": rec[:, 7].copy(), "information": rec[:, 8:44].reshape(n_hyp, 6, 6).copy(), "b": rec[:, 44:50].copy()}
+        ok = np.flatnonzero(out["n_used"] >= prm.min_points)
+        out["best"] = int(ok[np.argmin(out["cost"][ok])]) if ok.size else -1
+        if per_point:
+            out["obj"], out["dist"] = obj, dist
+        if trace:
+            iu = np.triu_indices(6)
+            hh = np.zeros((n_hyp, iters, 6, 6), np.float64)
+            hh[:, :, iu[0], iu[1]] = tr[:, :, 20:41]
+            hh[:, :, iu[1], iu[0]] = tr[:, :, 20:41]
+            out["trace"] = {"pose": tr[:, :, :16].reshape(n_hyp, iters, 4, 4).copy(), "decision": tr[:, :, 16].astype(np.int32), "cost": tr[:, :, 17].copy(),
+                            "lambda": tr[:, :, 18].copy(), "n_used": tr[:, :, 19].astype(np.int64), "H": hh, "b": tr[:, :, 41:47].copy(),
+                            "xi": tr[:, :, 47:53].copy()}
+        return out
+
+    def align_stats(self):
+        """Counts of the last align_to_map on this engine (dsp_map_align_last_stats), summed over its evaluations."""
+        c = np.zeros(5, np.int64)
+        L.check(L.load().dsp_map_align_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_align_last_stats")
+        return {"rows": int(c[0]), "tiles": int(c[1]), "chunks": int(c[2]), "passes": int(c[3]), "evaluations": int(c[4])}
+
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
         c = np.zeros(5, np.int64)

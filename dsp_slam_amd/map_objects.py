@@ -54,6 +54,16 @@ def query_points(engine, objects, pts_world, normals=False):
     return with_ids(res, [o["id"] for o in objects])
 
 
+def localise(engine, objects, pts_sensor, t_world_sensor0, weights=None, trace=False, **params):
+    """Engine.align_to_map on the list read_map_objects returns: the sensor-to-world pose that puts the sensor-frame points on the map's
+    surfaces, one Gauss-Newton run per initial pose of t_world_sensor0.  The result dict of Engine.align_to_map with per-point `obj` /
+    `dist` at every returned pose, plus `id`: the map's object id per hypothesis and point, -1 where obj is -1."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    res = engine.align_to_map(poses, [o["code"] for o in objects], pts_sensor, t_world_sensor0, weights=weights, trace=trace, per_point=True, **params)
+    return with_ids(res, [o["id"] for o in objects])
+
+
 def with_ids(result, ids):
     """result (an Engine.query_map dict) with `id` added: ids[obj] per point, -1 where obj is -1."""
     out = dict(result)

@@ -343,6 +343,71 @@ int dsp_debug_query_chunk_rows(dsp_handle* h, int64_t rows);
  * The results of a call do not depend on it. */
 int dsp_debug_query_timing(dsp_handle* h, int on, double* ms2);
 
+/* ---- map alignment: where is the sensor, given points in its frame and the map?  Batched SE(3) Gauss-Newton ---------------------------
+ * n_hyp initial sensor-to-world poses (hypotheses: a relocaliser's seeds, the yaw alternatives of the mono path) are refined against the
+ * map's decoded surfaces.  All hypotheses share the n_pts sensor-frame points and their optional weights (NULL = ones) and are
+ * independent of each other: a call with n_hyp hypotheses returns what n_hyp calls with one would, byte for byte.
+ * One evaluation of a hypothesis at pose T: p_w = T p_s (T's [R | t] rounded once to fp32, nested fmaf); the map query of p_w gives the
+ * winning object and d = sdf s; the winner's gradient rotated to the world and multiplied by s gives g_w (NOT normalised: it is the
+ * jacobian of d).  A point is valid if p_w is finite and its weight > 0; used if it is valid, has a winner, d and g_w are finite and
+ * |d| <= max_dist.  Cost: the truncated Huber F = sum w rho~ / sum_valid w, rho(d) = d^2 for |d| <= huber, else huber (2 |d| - huber);
+ * a valid point that is not used contributes the constant rho(max_dist), so costs at different poses are comparable.  System, fp64:
+ * J = [g_w, p_w x g_w] for the left perturbation T <- exp(xi) T, xi = [v, omega]; H = sum w wh J J^T, b = -sum w wh J d with the IRLS
+ * weight wh = 1 for |d| <= huber, else huber / |d|.  The sums are one written tree (csrc/align_math.h), the same bits whatever the
+ * passes, chunks or grid; no float atomics.  Step, host fp64: Cholesky of H + (damp + lambda) I, T_trial = exp_se3(xi) T.
+ * Loop, by the conventions of dsp_batch_step_control: `iterations` is the number of evaluations (1 = evaluate only); at most
+ * iterations - 1 steps are made and the state returned is the best EVALUATED one, with the record of that state.  Step control all zero
+ * = off: every trial is accepted (plain damped Gauss-Newton, lambda = 0), and a trial with fewer than min_points used points or a failed
+ * factorisation ends the hypothesis with that status at that state.  With step control on, the rule of dsp_debug_step_rule decides on F;
+ * a rejected trial solves the saved system again with the larger lambda; a trial without support is a rejection; a factorisation that
+ * fails raises lambda like a rejection and is repeated (DSP_ALIGN_SINGULAR once lambda_max fails too); a FIRST evaluation without
+ * support ends the hypothesis.  Convergence is tested on the solved step: max |v| < trans_tol and max |omega| < rot_tol (strict: 0
+ * stops nothing) gives DSP_ALIGN_CONVERGED and no step.  A hypothesis that has ended is never evaluated again and costs no decoder rows.
+ *
+ * dsp_map_align: the map as dsp_map_query takes and checks it; pts_sensor n_pts x 3; weights NULL or n_pts (finite, >= 0);
+ * t_world_sensor0 n_hyp x 16 doubles, row-major 4 x 4, rigid.  Outputs: t_world_sensor n_hyp x 16 doubles; record n_hyp x
+ * DSP_ALIGN_RECORD doubles {status, evaluations, accepted steps, cost at the first state, cost at the returned state, used points, sum of
+ * valid weights, lambda, H 6 x 6 (undamped: the information matrix of xi at the returned state), b 6}; obj / dist (optional, both or
+ * neither, n_hyp x n_pts): the query's answer per point at the returned state; trace (optional, n_hyp x iterations x DSP_ALIGN_TRACE
+ * doubles, zero where nothing was evaluated) per evaluation {pose evaluated 16, decision (1 accepted, 2 rejected), cost, lambda behind
+ * the decision, used points, H 21 (upper triangle, row-major), b 6, xi solved 6}.  n_hyp, n_pts and n_obj may be 0; with no points or
+ * no objects every hypothesis returns DSP_ALIGN_NO_SUPPORT with its input pose.  DSP_E_ARG: a map dsp_map_query refuses; an initial pose
+ * that is not finite, has a bottom row other than 0 0 0 1, whose linear part is off a rotation by more than 1e-4 or whose scale is off 1
+ * by more than 1e-4; a negative or non-finite weight; n_hyp x n_pts > 2^31 - 1; params that dsp_align_params_default's comment refuses. */
+#define DSP_ALIGN_OK 0           /* the iterations ran out */
+#define DSP_ALIGN_CONVERGED 1
+#define DSP_ALIGN_NO_SUPPORT 2   /* fewer than min_points used points */
+#define DSP_ALIGN_SINGULAR 3     /* a pivot of the Cholesky factorisation was not positive or not finite */
+#define DSP_ALIGN_RECORD 50
+#define DSP_ALIGN_TRACE 53
+typedef struct dsp_align_params {
+    int32_t iterations;          /* evaluations, >= 1 */
+    int32_t min_points;          /* >= 6 */
+    double max_dist;             /* the gate on |d|, world units; finite */
+    double huber;                /* 0 < huber <= max_dist */
+    double damp;                 /* >= 0, finite: added to H's diagonal in every solve */
+    double trans_tol, rot_tol;   /* >= 0, not NaN */
+    double lambda0, up, down, lambda_min, lambda_max;   /* all zero = off; otherwise dsp_batch_step_control's checks */
+} dsp_align_params;
+/* 10 evaluations, min_points 6, max_dist 0.3, huber 0.05, damp 0, both tolerances 1e-6, step control off */
+void dsp_align_params_default(dsp_align_params* p);
+int dsp_map_align(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_sensor, const float* weights,
+                  int64_t n_pts, const double* t_world_sensor0, int64_t n_hyp, const dsp_align_params* params, double* t_world_sensor,
+                  double* record, int32_t* obj, float* dist, double* trace);
+/* Counts of the last dsp_map_align on this handle: counts5 = {candidate rows, decoder tiles, chunks, point passes (all summed over its
+ * evaluations), device evaluations (one per iteration in which any hypothesis was live)}. */
+int dsp_map_align_last_stats(dsp_handle* h, int64_t* counts5);
+/* Host only, no handle: csrc/align_math.h on arrays.  dsp_debug_align_rows: n points' p_w (n x 3), obj, d, g_w (n x 3) and w (NULL =
+ * ones) -> sums30 = {H 21, b 6, sum w rho~, sum_valid w, used points} through the written tree.  dsp_debug_align_step: H (6 x 6, the
+ * upper triangle is read), b, damp, lambda, T (16) -> status (DSP_ALIGN_OK or DSP_ALIGN_SINGULAR), xi (6) and T_trial = exp_se3(xi) T
+ * (16; both untouched when singular).  dsp_debug_align_check: DSP_E_ARG for params, initial poses or weights (NULL = none) that
+ * dsp_map_align refuses, by the very checks it makes before it touches the device. */
+int dsp_debug_align_check(const dsp_align_params* params, const double* t_world_sensor0, int64_t n_hyp, const float* weights, int64_t n_pts);
+int dsp_debug_align_rows(int64_t n, const float* pts_world, const int32_t* obj, const float* dist, const float* grad_world, const float* weights,
+                         double huber, double max_dist, double* sums30);
+int dsp_debug_align_step(const double* H36, const double* b6, double damp, double lambda, const double* t16, int32_t* status, double* xi6,
+                         double* t_trial16);
+
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,

@@ -9,10 +9,31 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdspgn.so")
-SOURCES = ["mlp_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "gn_kernels.hip", "mesh_kernels.hip", "surface_kernels.hip", "query_kernels.hip", "align_kernels.hip", "dsp_gn.hip",
-           "decoder_pack.hip", "decoder_pack_abi.hip", "pose_graph.cpp"]
-HEADERS = [os.path.join(CSRC, "dsp_internal.h"), os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "prior_math.h"), os.path.join(CSRC, "step_rule.h"), os.path.join(CSRC, "report_math.h"), os.path.join(CSRC, "surface_math.h"), os.path.join(CSRC, "query_math.h"), os.path.join(CSRC, "align_math.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_lp_common.h"), os.path.join(CSRC, "gn_solve_body.h"), os.path.join(CSRC, "gn_posterior_body.h"), os.path.join(ROOT, "include", "dsp_gn.h"),
-           os.path.join(CSRC, "batch_tokens.h"), os.path.join(CSRC, "decoder_pack.h"), os.path.join(CSRC, "host_common.h"), os.path.join(ROOT, "include", "dsp_pose_graph.h")]
+SOURCES = [
+    "mlp_kernel.hip",
+    "mlp_split_kernel.hip",
+    "mlp_cluster_kernel.hip",
+    "mlp_lp_kernel.hip",
+    "mlp_lpj_kernel.hip",
+    "gn_kernels.hip",
+    "mesh_kernels.hip",
+    "surface_kernels.hip",
+    "query_kernels.hip",
+    "align_kernels.hip",
+    "dsp_gn.hip",
+    "decoder_calls.hip",
+    "mesh_host.hip",
+    "map_host.hip",
+    "gather.hip",
+    "decoder_pack.hip",
+    "decoder_pack_abi.hip",
+    "pose_graph.cpp",
+]
+
+
+def headers():
+    """Every header of the library: any of them newer than an object rebuilds it."""
+    return sorted(os.path.join(d, f) for d in (CSRC, os.path.join(ROOT, "include")) for f in os.listdir(d) if f.endswith(".h"))
 
 
 def _hipcc():
@@ -26,7 +47,7 @@ def is_stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + headers() + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -41,7 +62,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 def _compile_one(hipcc, src, verbose):
     obj = os.path.join(OBJ_DIR, src + ".o")
-    deps = [os.path.join(CSRC, src)] + HEADERS + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, src)] + headers() + [os.path.abspath(__file__)]
     if src == "dsp_gn.hip":
         deps.append(os.path.join(LIB_DIR, "build_info.h"))
     if os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in deps):

@@ -264,7 +264,7 @@ __device__ __forceinline__ int4 direct_tile(const DirectTiles& d, const DirectLi
 #endif
 static_assert(sizeof(ObjState) % 16 == 0, "ObjState is addressed as float4-aligned rows");
 
-// Prepass margin as a function of the code's largest entry: calibrate_prepass (dsp_gn.hip) measures the largest |sdf_lp - sdf_fp32|
+// Prepass margin as a function of the code's largest entry: calibrate_prepass (decoder_calls.hip) measures the largest |sdf_lp - sdf_fp32|
 // with codes drawn at each of these magnitudes; delta is interpolated between them (linear extrapolation above, capped at 0.5).
 constexpr int LP_NMAG = 5;
 struct LpDeltaTab {

@@ -9,7 +9,7 @@
 #include <cstdint>
 
 namespace launch_plan {
-constexpr int TILE = 64, SPLIT_TILE = 16, LP_TILE = 128, LP_TILE_SMALL = 64;   // = TILE_PTS, SPLIT_TILE_PTS, LP_TILE_PTS(_SMALL) of dsp_internal.h (static_assert in dsp_gn.hip)
+constexpr int TILE = 64, SPLIT_TILE = 16, LP_TILE = 128, LP_TILE_SMALL = 64;   // = TILE_PTS, SPLIT_TILE_PTS, LP_TILE_PTS(_SMALL) of dsp_internal.h (static_assert in batch.h)
 
 // tri-state settings: -1 automatic, 0 off, 1 on (fused_bookkeeping: 2 = the wave form), pinned through dsp_batch_set_debug (DSP_DBG_*)
 struct PlanInputs {

@@ -1,0 +1,542 @@
+// The object map on the host: signed distance and normal of world points (dsp_map_query) and the alignment of a point cloud to the map
+// (dsp_map_align), which runs the query's core; with their C ABI.
+#include "decoder_calls.h"
+#include "decoder_pack.h"
+#include "query_math.h"     // constants only: the arithmetic is compiled in query_kernels.hip (contraction off)
+#include "align_math.h"     // constants only, likewise (align_kernels.hip)
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// map query (dsp_map_query; arithmetic: query_math.h, kernels: query_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// Both budgets are fixed, whatever the device has free.  A chunk holds at most QUERY_CHUNK_BYTES of decoder output rows, counted as
+// GRAD_STRIDE floats each in either decoder form (246 723 rows); a pass holds at most QUERY_PASS_PTS points, and fewer when the map is so
+// large that n_obj x ceil(points / 64) wave counts would exceed QUERY_WAVECNT_BYTES (from 8192 objects on).  QUERY_MAX_OBJ keeps a pass at
+// 64 points or more.
+constexpr size_t QUERY_CHUNK_BYTES = (size_t)64 << 20;
+constexpr size_t QUERY_WAVECNT_BYTES = (size_t)64 << 20;
+constexpr int64_t QUERY_PASS_PTS = (int64_t)1 << 17;
+constexpr int64_t QUERY_MAX_OBJ = (int64_t)1 << 18;
+static_assert(QUERY_WAVECNT_BYTES / sizeof(int) / QUERY_MAX_OBJ >= 1, "a pass has at least one wave of points");
+
+// what one chunk uploads; kept until the stream has been synchronised behind the chunk's launches
+struct QueryChunk {
+    int o0 = 0, nc = 0, n_rows = 0, nt = 0;     // objects [o0, o0 + nc) of the map, rows and tiles of the chunk
+    std::vector<int> base;                      // per object of the chunk: chunk row of its first candidate (negative: the chunk starts inside it)
+    std::vector<int4> tiles;                    // {first row, count, code-bias slot, 0}
+    std::vector<float> cb;                      // code biases of the objects that have rows in the chunk, in slot order
+};
+
+// the chunks of one pass from the objects' candidate counts: consecutive objects, or a range of one object's candidates, of at most `budget` rows
+std::vector<QueryChunk> query_plan(const dsp_handle* h, const float* codes, const std::vector<int>& cnt, int64_t budget) {
+    std::vector<QueryChunk> plan;
+    const int64_t n_obj = (int64_t)cnt.size();
+    int64_t o = 0, used = 0;                    // the next candidate without a chunk: candidate `used` of object o
+    for (;;) {
+        while (o < n_obj && used >= cnt[o]) { ++o; used = 0; }
+        if (o == n_obj) break;
+        plan.emplace_back();
+        QueryChunk& c = plan.back();
+        c.o0 = (int)o;
+        int64_t rows = 0;
+        int slot = 0;
+        while (o < n_obj && rows < budget) {
+            const int64_t take = std::min<int64_t>(cnt[o] - used, budget - rows);
+            c.base.push_back((int)(rows - used));
+            if (take > 0) {
+                for (int64_t i = 0; i < take; i += TILE_PTS) c.tiles.push_back(make_int4((int)(rows + i), (int)std::min<int64_t>(TILE_PTS, take - i), slot, 0));
+                c.cb.resize((size_t)(slot + 1) * 2 * WIDTH);
+                code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + o * CODE_LEN, c.cb.data() + (size_t)slot * 2 * WIDTH);
+                ++slot;
+            }
+            rows += take;
+            used += take;
+            if (used < cnt[o]) break;           // the budget ends inside this object: the next chunk goes on from `used`
+            ++o;
+            used = 0;
+        }
+        c.nc = (int)c.base.size();
+        c.n_rows = (int)rows;
+        c.nt = (int)c.tiles.size();
+    }
+    return plan;
+}
+
+// dsp_debug_query_timing: HIP events on the handle's stream around a whole call (first and last mark) and around every decoder launch (the
+// pairs in between)
+struct QueryTimer {
+    bool on;
+    hipStream_t s;
+    std::vector<hipEvent_t> ev;
+    ~QueryTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void mark() {
+        if (!on) return;
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        ev.push_back(e);
+        HIP_TRY(hipEventRecord(e, s));
+    }
+    // after the stream has been synchronised behind the last mark: ms2 = {decoder launches, whole call}
+    void read(double* ms2) {
+        ms2[0] = ms2[1] = 0.0;
+        if (!on || ev.size() < 2) return;
+        float ms = 0.f;
+        for (size_t k = 1; k + 1 < ev.size(); k += 2) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+            ms2[0] += ms;
+        }
+        HIP_TRY(hipEventElapsedTime(&ms, ev.front(), ev.back()));
+        ms2[1] = ms;
+    }
+};
+
+// the device arrays of one query: n_pts world points (packed float3) and the object table in, per-point results out
+struct QueryDev {
+    const float* pts;
+    const float* tab;
+    float* bound;
+    unsigned long long* best;
+    int* obj;
+    float* dist;
+    float* normal;              // null: no unit normals
+};
+
+// The device-resident query: passes, chunks, decoder launches, reduce and finish on the handle's stream, device arrays in and out.
+// jacobian: the decoder's jacobian form (required by d.normal and by a hook that reads the rows' gradients).  behind_reduce (may be empty)
+// is called behind every chunk's launch_query_reduce, while the chunk's rows (h->s_out) and row_meta are in place.  Synchronises once per
+// pass (the counts' read-back); the caller synchronises behind it before `plan` (the last pass's uploads) dies.  stats4 += {rows, tiles,
+// chunks, passes}.  n_pts > 0, n_obj > 0.
+void query_core(dsp_handle* h, const float* codes, int64_t n_obj, int64_t n_pts, const QueryDev& d, bool jacobian, std::vector<QueryChunk>& plan,
+                QueryTimer& timer, int64_t* stats4, const std::function<void(const QueryChunk&)>& behind_reduce) {
+    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : (int64_t)(QUERY_CHUNK_BYTES / (GRAD_STRIDE * sizeof(float)));
+    const int64_t pass_pts = std::min<int64_t>(QUERY_PASS_PTS, (int64_t)(QUERY_WAVECNT_BYTES / sizeof(int) / (size_t)n_obj) * 64);
+    std::vector<int> cnt((size_t)n_obj);
+    h->q_cnt.ensure((size_t)n_obj);
+    h->s_ntiles.ensure(1);
+    h->s_clk.ensure(4);
+    for (int64_t p0 = 0; p0 < n_pts; p0 += pass_pts) {
+        const int n = (int)std::min(pass_pts, n_pts - p0);
+        const int n_waves = (n + 63) / 64;
+        h->q_wave_cnt.ensure((size_t)n_obj * n_waves);
+        HIP_TRY(launch_query_count(d.pts, p0, n, d.tab, (int)n_obj, n_waves, h->q_wave_cnt.p, h->q_cnt.p, d.bound, d.best, h->stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), h->q_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));       // the counts; everything the previous pass uploaded has been consumed
+        plan = query_plan(h, codes, cnt, budget);
+        stats4[3] += 1;
+        size_t max_rows = 0, max_nt = 0, max_nc = 0, max_cb = 0;
+        for (const QueryChunk& c : plan) {
+            max_rows = std::max<size_t>(max_rows, c.n_rows); max_nt = std::max<size_t>(max_nt, c.nt);
+            max_nc = std::max<size_t>(max_nc, c.nc); max_cb = std::max(max_cb, c.cb.size());
+        }
+        if (plan.empty()) continue;
+        h->s_pts.ensure(max_rows);
+        h->s_out.ensure(max_rows * (jacobian ? GRAD_STRIDE : 1));
+        h->q_row_meta.ensure(max_rows);
+        h->s_tiles.ensure(max_nt);
+        h->s_cbias.ensure(max_cb);
+        h->q_base.ensure(max_nc);
+        for (const QueryChunk& c : plan) {
+            HIP_TRY(hipMemcpyAsync(h->s_cbias.p, c.cb.data(), c.cb.size() * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->s_tiles.p, c.tiles.data(), c.nt * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->s_ntiles.p, &c.nt, 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->q_base.p, c.base.data(), c.nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(launch_query_fill(d.pts, p0, n, d.tab, c.o0, c.nc, h->q_base.p, n_waves, h->q_wave_cnt.p, c.n_rows, h->s_pts.p,
+                                      h->q_row_meta.p, h->stream));
+            MlpArgs a = make_mlp_args(h, jacobian ? 2 : 0);
+            a.n_tiles = h->s_ntiles.p;
+            a.tiles = h->s_tiles.p;
+            a.pts = h->s_pts.p;
+            a.code_bias = h->s_cbias.p;
+            a.code_bias_stride = 2 * WIDTH;
+            a.out_sdf = h->s_out.p;
+            a.out_grad = h->s_out.p;
+            a.clk = h->s_clk.p;
+            timer.mark();
+            HIP_TRY(launch_mlp(jacobian ? 2 : 0, a, std::min(c.nt, h->n_cu), h->stream));
+            timer.mark();
+            HIP_TRY(launch_query_reduce(h->s_out.p, jacobian, h->q_row_meta.p, c.n_rows, d.tab, (int)n_obj, n_pts, d.best, d.normal, h->stream));
+            if (behind_reduce) behind_reduce(c);
+            stats4[0] += c.n_rows;
+            stats4[1] += c.nt;
+            stats4[2] += 1;
+        }
+    }
+    HIP_TRY(launch_query_finish(d.best, n_pts, d.obj, d.dist, d.normal, h->stream));
+}
+
+// synchronises the stream when it goes: declared behind the call's device blocks and host uploads, so that it is destroyed before them,
+// also when an allocation further down throws
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// tab: n_obj x query_math::OBJ_STRIDE floats (host).  Outputs are host arrays; normal null = the forward decoder form.  Upload, query_core,
+// download; synchronises once per pass (the counts' read-back) and once at the end.
+void query_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* pts_world, int64_t n_pts, int32_t* obj,
+               float* dist, float* bound, float* normal) {
+    for (auto& c : h->q_stats) c = 0;
+    if (n_pts == 0) return;
+    if (n_obj == 0) {
+        for (int64_t i = 0; i < n_pts; ++i) {
+            obj[i] = -1;
+            dist[i] = bound[i] = INFINITY;
+            if (normal) normal[3 * i] = normal[3 * i + 1] = normal[3 * i + 2] = 0.f;
+        }
+        return;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    DevBuf<float> q_pts, q_tab, q_bound, q_dist, q_normal;
+    DevBuf<unsigned long long> q_best;
+    DevBuf<int> q_obj;
+    std::vector<QueryChunk> plan;   // the uploads of the pass in flight are copied from here
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    q_pts.alloc((size_t)n_pts * 3);
+    q_tab.alloc(tab.size());
+    q_bound.alloc((size_t)n_pts);
+    q_dist.alloc((size_t)n_pts);
+    q_obj.alloc((size_t)n_pts);
+    q_best.alloc((size_t)n_pts);
+    if (normal) q_normal.alloc((size_t)n_pts * 3);
+    HIP_TRY(hipMemcpyAsync(q_pts.p, pts_world, (size_t)n_pts * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const QueryDev d{q_pts.p, q_tab.p, q_bound.p, q_best.p, q_obj.p, q_dist.p, normal ? q_normal.p : nullptr};
+    query_core(h, codes, n_obj, n_pts, d, normal != nullptr, plan, timer, h->q_stats, {});
+    HIP_TRY(hipMemcpyAsync(obj, q_obj.p, (size_t)n_pts * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dist, q_dist.p, (size_t)n_pts * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(bound, q_bound.p, (size_t)n_pts * 4, hipMemcpyDeviceToHost, h->stream));
+    if (normal) HIP_TRY(hipMemcpyAsync(normal, q_normal.p, (size_t)n_pts * 12, hipMemcpyDeviceToHost, h->stream));
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));           // `plan` (the last pass's uploads) lives until here
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+}
+
+// the map's host table (query_math::OBJ_STRIDE floats per object) as dsp_map_query and dsp_map_align check and build it
+std::vector<float> query_table(const dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj) {
+    if (n_obj > QUERY_MAX_OBJ) throw std::invalid_argument("map query too large (split the request)");
+    std::vector<float> tab((size_t)n_obj * query_math::OBJ_STRIDE, 0.f);
+    for (int64_t o = 0; o < n_obj; ++o) {
+        float* e = tab.data() + o * query_math::OBJ_STRIDE;
+        if (!query_invert_host(t_world_obj + 16 * o, e, e + 12))
+            throw std::invalid_argument("t_world_obj: a pose is not a finite Sim(3) (rotation times a positive scale, bottom row 0 0 0 1)");
+        // an object whose code is not finite never wins: the decoder's ReLUs may turn it into finite values, so its distances are made NaN
+        bool code_ok = true;
+        for (int k = 0; k < h->code_len; ++k) code_ok = code_ok && std::isfinite(codes[o * CODE_LEN + k]);
+        e[13] = code_ok ? e[12] : std::nanf("");
+    }
+    return tab;
+}
+
+// ------------------------------------------------------------------------------------------------
+// map alignment (dsp_map_align; arithmetic: align_math.h, kernels: align_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+const char* align_check_params(const dsp_align_params& p) {
+    if (p.iterations < 1) return "align: iterations must be >= 1";
+    if (p.min_points < 6) return "align: min_points must be >= 6";
+    if (!std::isfinite(p.max_dist) || !std::isfinite(p.huber) || !(p.huber > 0.0) || !(p.huber <= p.max_dist)) return "align: 0 < huber <= max_dist, both finite";
+    if (!std::isfinite(p.damp) || p.damp < 0.0) return "align: damp must be finite and >= 0";
+    if (!(p.trans_tol >= 0.0) || !(p.rot_tol >= 0.0)) return "align: the tolerances must be >= 0";
+    const step_rule::Params sp{p.lambda0, p.up, p.down, p.lambda_min, p.lambda_max};
+    return step_rule::is_off(sp) ? nullptr : step_rule::check(sp);
+}
+
+// what dsp_map_align refuses before it touches the device, besides the map: nullptr, or what is wrong
+const char* align_check_inputs(const dsp_align_params& p, const double* T0, int64_t n_hyp, const float* weights, int64_t n_pts) {
+    if (const char* why = align_check_params(p)) return why;
+    if (n_hyp > 0 && n_pts > (int64_t)0x7fffffff / n_hyp) return "align: n_hyp x n_pts exceeds 2^31 - 1 (split the request)";
+    float rt[12];
+    for (int64_t k = 0; k < n_hyp; ++k)
+        if (!align_check_pose_host(T0 + 16 * k, rt)) return "t_world_sensor0: a pose is not a finite rigid transform (rotation, unit scale, bottom row 0 0 0 1)";
+    if (weights)
+        for (int64_t i = 0; i < n_pts; ++i)
+            if (!(weights[i] >= 0.f) || !std::isfinite(weights[i])) return "align: weights must be finite and >= 0";
+    return nullptr;
+}
+
+// one hypothesis on the host: the accepted state with its sums, and the pose to evaluate next
+struct AlignHyp {
+    double T_acc[16], T_eval[16];
+    double S[align_math::NSUM];         // the sums at T_acc
+    double F_acc = 0.0, F0 = 0.0, lam = 0.0;
+    bool live = true, has_acc = false;
+    int status = DSP_ALIGN_OK, evals = 0, steps = 0;
+};
+
+void align_write(const AlignHyp& a, double* T_out, double* rec) {
+    memcpy(T_out, a.T_acc, sizeof a.T_acc);
+    rec[0] = a.status; rec[1] = a.evals; rec[2] = a.steps; rec[3] = a.F0; rec[4] = a.F_acc;
+    rec[5] = a.S[align_math::IDX_N]; rec[6] = a.S[align_math::IDX_W]; rec[7] = a.lam;
+    int k = align_math::IDX_H;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) rec[8 + 6 * i + j] = rec[8 + 6 * j + i] = a.S[k++];
+    for (int i = 0; i < 6; ++i) rec[44 + i] = a.S[align_math::IDX_B + i];
+}
+
+// Points and weights are uploaded once; per evaluation the host sends the hypotheses' fp32 poses and reads the query's candidate counts
+// (once per pass) and align_math::NSUM doubles per hypothesis.  The step lives on the host.
+void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* pts, const float* weights, int64_t n_pts,
+               const double* T0, int64_t n_hyp, const dsp_align_params& prm, double* T_out, double* record, int32_t* obj, float* dist, double* trace) {
+    constexpr int NS = align_math::NSUM;
+    for (auto& c : h->a_stats) c = 0;
+    const step_rule::Params sp{prm.lambda0, prm.up, prm.down, prm.lambda_min, prm.lambda_max};
+    const bool step_on = !step_rule::is_off(sp);
+    const int iters = prm.iterations;
+    std::vector<AlignHyp> hyp((size_t)n_hyp);
+    for (int64_t k = 0; k < n_hyp; ++k) {
+        memcpy(hyp[k].T_acc, T0 + 16 * k, sizeof hyp[k].T_acc);
+        memcpy(hyp[k].T_eval, T0 + 16 * k, sizeof hyp[k].T_eval);
+        for (double& s : hyp[k].S) s = 0.0;
+    }
+    if (trace) std::fill(trace, trace + (size_t)n_hyp * iters * DSP_ALIGN_TRACE, 0.0);
+    if (n_hyp == 0) return;
+    if (n_pts == 0 || n_obj == 0) {             // nothing to evaluate: no support at the input pose
+        double zero[NS] = {};
+        for (int64_t k = 0; k < n_hyp; ++k) {
+            hyp[k].status = DSP_ALIGN_NO_SUPPORT;
+            hyp[k].F0 = hyp[k].F_acc = align_cost_host(zero, prm.huber, prm.max_dist);
+            align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
+        }
+        if (obj)
+            for (int64_t r = 0; r < n_hyp * n_pts; ++r) { obj[r] = -1; dist[r] = INFINITY; }
+        return;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_rows = n_hyp * n_pts, nb = align_gram_blocks(n_pts);
+    DevBuf<float> a_pts, a_w, a_hyp, a_grad, q_tab, q_pw, q_bound, q_dist, r_dist;
+    DevBuf<unsigned long long> q_best;
+    DevBuf<int> q_obj, r_obj;
+    DevBuf<double> a_slab, a_sums;
+    std::vector<QueryChunk> plan;               // the uploads of the pass in flight are copied from here ...
+    std::vector<float> hyp_tab((size_t)n_hyp * ALIGN_HYP_STRIDE, 0.f);      // ... and the evaluation's poses from here
+    std::vector<double> sums((size_t)n_hyp * NS, 0.0);
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    a_pts.alloc((size_t)n_pts * 3);
+    if (weights) a_w.alloc((size_t)n_pts);
+    a_hyp.alloc(hyp_tab.size());
+    a_grad.alloc((size_t)n_rows * 3);
+    q_tab.alloc(tab.size());
+    q_pw.alloc((size_t)n_rows * 3);
+    q_bound.alloc((size_t)n_rows);
+    q_dist.alloc((size_t)n_rows);
+    q_obj.alloc((size_t)n_rows);
+    q_best.alloc((size_t)n_rows);
+    if (obj) { r_obj.alloc((size_t)n_rows); r_dist.alloc((size_t)n_rows); }
+    a_slab.alloc((size_t)n_hyp * nb * NS);
+    a_sums.alloc(sums.size());
+    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_pts * 12, hipMemcpyHostToDevice, h->stream));
+    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_pts * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const QueryDev d{q_pw.p, q_tab.p, q_bound.p, q_best.p, q_obj.p, q_dist.p, nullptr};
+    const std::function<void(const QueryChunk&)> winner = [&](const QueryChunk& c) {
+        HIP_TRY(launch_align_winner(h->s_out.p, h->q_row_meta.p, c.n_rows, q_tab.p, (int)n_obj, n_rows, q_best.p, a_grad.p, h->stream));
+    };
+    auto end = [](AlignHyp& a, int status) { a.live = false; a.status = status; };
+    for (int e = 0; e < iters; ++e) {
+        bool any = false;
+        for (int64_t k = 0; k < n_hyp; ++k) {   // the stream is idle here: the previous evaluation's read-back has been waited for
+            float* t = hyp_tab.data() + k * ALIGN_HYP_STRIDE;
+            for (int i = 0; i < 12; ++i) t[i] = (float)hyp[k].T_eval[i];
+            t[12] = hyp[k].live ? 1.f : 0.f;
+            any = any || hyp[k].live;
+        }
+        if (!any) break;
+        HIP_TRY(hipMemcpyAsync(a_hyp.p, hyp_tab.data(), hyp_tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(launch_align_transform(a_pts.p, n_pts, a_hyp.p, 0, n_rows, q_pw.p, h->stream));
+        query_core(h, codes, n_obj, n_rows, d, true, plan, timer, h->a_stats, winner);
+        HIP_TRY(launch_align_gram(q_pw.p, q_obj.p, q_dist.p, a_grad.p, weights ? a_w.p : nullptr, n_pts, (int)n_hyp, a_hyp.p, prm.huber, prm.max_dist,
+                                  a_slab.p, a_sums.p, h->stream));
+        HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));       // the sums; `plan` and hyp_tab have been consumed
+        h->a_stats[4] += 1;
+        for (int64_t k = 0; k < n_hyp; ++k) {
+            AlignHyp& a = hyp[k];
+            if (!a.live) continue;
+            const double* S = sums.data() + k * NS;
+            const double F = align_cost_host(S, prm.huber, prm.max_dist);
+            const bool support = S[align_math::IDX_N] >= (double)prm.min_points;
+            double* tr = trace ? trace + ((size_t)k * iters + e) * DSP_ALIGN_TRACE : nullptr;
+            a.evals += 1;
+            if (e == 0) a.F0 = F;
+            int dec = step_rule::ACCEPTED;
+            if (step_on)
+                dec = !a.has_acc ? step_rule::decide(true, F, 0.0, sp, a.lam)
+                                 : step_rule::decide(false, support ? F : (double)INFINITY, a.F_acc, sp, a.lam);
+            if (dec == step_rule::ACCEPTED) {
+                if (a.has_acc) a.steps += 1;
+                memcpy(a.T_acc, a.T_eval, sizeof a.T_acc);
+                memcpy(a.S, S, sizeof a.S);
+                a.F_acc = F;
+                a.has_acc = true;
+                if (obj) {      // the per-point outputs belong to the returned state
+                    HIP_TRY(hipMemcpyAsync(r_obj.p + k * n_pts, q_obj.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
+                    HIP_TRY(hipMemcpyAsync(r_dist.p + k * n_pts, q_dist.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
+                }
+            }
+            if (tr) {
+                memcpy(tr, a.T_eval, sizeof a.T_eval);
+                tr[16] = dec; tr[17] = F; tr[18] = a.lam; tr[19] = S[align_math::IDX_N];
+                memcpy(tr + 20, S, 27 * sizeof(double));
+            }
+            // the step from the accepted state
+            if (a.S[align_math::IDX_N] < (double)prm.min_points) { end(a, DSP_ALIGN_NO_SUPPORT); continue; }
+            double H[36], xi[6];
+            int q = align_math::IDX_H;
+            for (int i = 0; i < 6; ++i)
+                for (int j = i; j < 6; ++j) H[6 * i + j] = H[6 * j + i] = a.S[q++];
+            bool solved = false;
+            for (int tries = 0; !solved; ++tries) {
+                solved = align_solve_host(H, a.S + align_math::IDX_B, prm.damp, a.lam, xi);
+                if (solved || !step_on || tries >= 64 || !(a.lam < sp.lambda_max)) break;
+                a.lam = fmin(fmax(a.lam, sp.lambda_min) * sp.up, sp.lambda_max);        // a failed factorisation: lambda grows like after a rejection
+            }
+            if (tr) tr[18] = a.lam;
+            if (!solved) { end(a, DSP_ALIGN_SINGULAR); continue; }
+            if (tr) memcpy(tr + 47, xi, sizeof xi);
+            const double mv = fmax(fmax(fabs(xi[0]), fabs(xi[1])), fabs(xi[2])), mw = fmax(fmax(fabs(xi[3]), fabs(xi[4])), fabs(xi[5]));
+            if (mv < prm.trans_tol && mw < prm.rot_tol) { end(a, DSP_ALIGN_CONVERGED); continue; }
+            if (e == iters - 1) { end(a, DSP_ALIGN_OK); continue; }
+            align_apply_step_host(xi, a.T_acc, a.T_eval);
+        }
+    }
+    if (obj) {
+        HIP_TRY(hipMemcpyAsync(obj, r_obj.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(dist, r_dist.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+    for (int64_t k = 0; k < n_hyp; ++k) align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsp_map_query(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, int64_t n_pts, int32_t flags,
+                  int32_t* obj, float* dist, float* bound, float* normal) {
+    if (!h || n_obj < 0 || n_pts < 0 || (flags & ~DSP_QUERY_NORMALS)) return DSP_E_ARG;
+    const bool normals = (flags & DSP_QUERY_NORMALS) != 0;
+    if ((n_obj > 0 && (!t_world_obj || !codes)) || (!normals && normal)) return DSP_E_ARG;
+    if (n_pts > 0 && (!pts_world || !obj || !dist || !bound || (normals && !normal))) return DSP_E_ARG;
+    return guarded(h, [&] {
+        if (n_pts > (int64_t)0x7fffffff) throw std::invalid_argument("map query too large (split the request)");
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        query_run(h, tab, codes, n_obj, pts_world, n_pts, obj, dist, bound, normal);
+    });
+}
+
+void dsp_align_params_default(dsp_align_params* p) {
+    if (!p) return;
+    *p = dsp_align_params{10, 6, 0.3, 0.05, 0.0, 1e-6, 1e-6, 0.0, 0.0, 0.0, 0.0, 0.0};
+}
+
+int dsp_map_align(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_sensor, const float* weights,
+                  int64_t n_pts, const double* t_world_sensor0, int64_t n_hyp, const dsp_align_params* params, double* t_world_sensor,
+                  double* record, int32_t* obj, float* dist, double* trace) {
+    if (!h || !params || n_obj < 0 || n_pts < 0 || n_hyp < 0 || (obj == nullptr) != (dist == nullptr)) return DSP_E_ARG;
+    if ((n_obj > 0 && (!t_world_obj || !codes)) || (n_pts > 0 && !pts_sensor) || (n_hyp > 0 && (!t_world_sensor0 || !t_world_sensor || !record)))
+        return DSP_E_ARG;
+    return guarded(h, [&] {
+        if (const char* why = align_check_inputs(*params, t_world_sensor0, n_hyp, weights, n_pts)) throw std::invalid_argument(why);
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        align_run(h, tab, codes, n_obj, pts_sensor, weights, n_pts, t_world_sensor0, n_hyp, *params, t_world_sensor, record, obj, dist, trace);
+    });
+}
+
+int dsp_map_align_last_stats(dsp_handle* h, int64_t* counts5) {
+    if (!h || !counts5) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts5, h->a_stats, sizeof h->a_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_align_check(const dsp_align_params* params, const double* t_world_sensor0, int64_t n_hyp, const float* weights, int64_t n_pts) {
+    if (!params || n_hyp < 0 || n_pts < 0 || (n_hyp > 0 && !t_world_sensor0)) return DSP_E_ARG;
+    return align_check_inputs(*params, t_world_sensor0, n_hyp, weights, n_pts) ? DSP_E_ARG : DSP_OK;
+}
+
+int dsp_debug_align_rows(int64_t n, const float* pts_world, const int32_t* obj, const float* dist, const float* grad_world, const float* weights,
+                         double huber, double max_dist, double* sums30) {
+    if (n < 0 || !sums30 || (n > 0 && (!pts_world || !obj || !dist || !grad_world))) return DSP_E_ARG;
+    if (!std::isfinite(max_dist) || !std::isfinite(huber) || !(huber > 0.0) || !(huber <= max_dist)) return DSP_E_ARG;
+    align_rows_host(n, pts_world, obj, dist, grad_world, weights, huber, max_dist, sums30);
+    return DSP_OK;
+}
+
+int dsp_debug_align_step(const double* H36, const double* b6, double damp, double lambda, const double* t16, int32_t* status, double* xi6,
+                         double* t_trial16) {
+    if (!H36 || !b6 || !t16 || !status || !xi6 || !t_trial16) return DSP_E_ARG;
+    if (!align_solve_host(H36, b6, damp, lambda, xi6)) {
+        *status = DSP_ALIGN_SINGULAR;
+        return DSP_OK;
+    }
+    *status = DSP_ALIGN_OK;
+    align_apply_step_host(xi6, t16, t_trial16);
+    return DSP_OK;
+}
+
+int dsp_map_query_last_stats(dsp_handle* h, int64_t* counts4) {
+    if (!h || !counts4) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts4, h->q_stats, sizeof h->q_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_query_invert(int64_t n_obj, const float* t_world_obj, float* rt_ow, float* scale) {
+    if (n_obj < 0 || (n_obj > 0 && (!t_world_obj || !rt_ow || !scale))) return DSP_E_ARG;
+    for (int64_t o = 0; o < n_obj; ++o)
+        if (!query_invert_host(t_world_obj + 16 * o, rt_ow + 12 * o, scale + o)) return DSP_E_ARG;
+    return DSP_OK;
+}
+
+int dsp_debug_query_candidates(int64_t n_obj, const float* rt_ow, const float* scale, int64_t n_pts, const float* pts_world, float* p_obj,
+                               unsigned char* inside, float* bound) {
+    if (n_obj < 0 || n_pts < 0 || (n_obj > 0 && (!rt_ow || !scale)) || (n_pts > 0 && !pts_world)) return DSP_E_ARG;
+    query_candidates_host(n_obj, rt_ow, scale, n_pts, pts_world, p_obj, inside, bound);
+    return DSP_OK;
+}
+
+int dsp_debug_query_select(int64_t n_rows, const float* sdf, const float* scale_of_row, const int32_t* obj_of_row, const int32_t* pt_of_row,
+                           int64_t n_pts, int32_t* obj, float* dist) {
+    if (n_rows < 0 || n_pts < 0 || (n_rows > 0 && (!sdf || !scale_of_row || !obj_of_row || !pt_of_row)) || (n_pts > 0 && (!obj || !dist))) return DSP_E_ARG;
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (pt_of_row[r] < 0 || pt_of_row[r] >= n_pts || obj_of_row[r] < 0) return DSP_E_ARG;
+    query_select_host(n_rows, sdf, scale_of_row, obj_of_row, pt_of_row, n_pts, obj, dist);
+    return DSP_OK;
+}
+
+int dsp_debug_query_timing(dsp_handle* h, int on, double* ms2) {
+    if (!h) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->q_timing = on != 0;
+    if (ms2) memcpy(ms2, h->q_ms, sizeof h->q_ms);
+    return DSP_OK;
+}
+
+int dsp_debug_query_chunk_rows(dsp_handle* h, int64_t rows) {
+    if (!h || rows < 0 || rows > ((int64_t)1 << 24)) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->q_chunk_rows = rows;
+    return DSP_OK;
+}
+
+}  // extern "C"

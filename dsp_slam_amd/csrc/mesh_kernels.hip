@@ -344,7 +344,7 @@ __global__ void k_grid_points(float4* pts, int n, float voxel_size, int regular)
                          __fadd_rn(__fmul_rn(fk, voxel_size), -1.f), 0.f);
 }
 
-// ---- batched extraction (extract_meshes_impl, dsp_gn.hip) -------------------------------------------------------------------
+// ---- batched extraction (extract_meshes_impl, mesh_host.hip) ----------------------------------------------------------------
 // n_obj volumes of the same grid, back to back.  The marching-cubes kernels below are the ones above with the object taken from
 // blockIdx.y; their block sums form ONE list (object-major) that k_mc_scan scans across the whole chunk, so every object's vertices
 // and faces land in their own contiguous range in the order dsp_extract_mesh produces.  Vertex ids in vidmap are chunk-global; faces

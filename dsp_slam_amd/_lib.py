@@ -166,6 +166,7 @@ SYMBOLS = [
     ("dsp_debug_query_candidates", C.c_int, [C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.POINTER(C.c_uint8), c_f32p]),
     ("dsp_debug_query_select", C.c_int, [C.c_int64, c_f32p, c_f32p, c_i32p, c_i32p, C.c_int64, c_i32p, c_f32p]),
     ("dsp_debug_query_chunk_rows", C.c_int, [_VP, C.c_int64]),
+    ("dsp_debug_query_plan", C.c_int, [C.c_int64, c_i32p, C.c_int64, C.c_int64, c_i64p, c_i32p, c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_query_timing", C.c_int, [_VP, C.c_int, c_f64p]),
     ("dsp_align_params_default", None, [C.POINTER(AlignParams)]),
     ("dsp_map_align", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f64p, C.c_int64, C.POINTER(AlignParams), c_f64p, c_f64p,

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <new>
 #include <stdexcept>
 #include <vector>
 
@@ -21,8 +22,8 @@ namespace {
 
 // Both budgets are fixed, whatever the device has free.  A chunk holds at most QUERY_CHUNK_BYTES of decoder output rows, counted as
 // GRAD_STRIDE floats each in either decoder form (246 723 rows); a pass holds at most QUERY_PASS_PTS points, and fewer when the map is so
-// large that n_obj x ceil(points / 64) wave counts would exceed QUERY_WAVECNT_BYTES (from 8192 objects on).  QUERY_MAX_OBJ keeps a pass at
-// 64 points or more.
+// large that n_obj x ceil(points / 64) wave counts would exceed QUERY_WAVECNT_BYTES (above 8192 objects).  QUERY_MAX_OBJ keeps a pass at
+// 64 waves of points or more.
 constexpr size_t QUERY_CHUNK_BYTES = (size_t)64 << 20;
 constexpr size_t QUERY_WAVECNT_BYTES = (size_t)64 << 20;
 constexpr int64_t QUERY_PASS_PTS = (int64_t)1 << 17;
@@ -34,13 +35,21 @@ struct QueryChunk {
     int o0 = 0, nc = 0, n_rows = 0, nt = 0;     // objects [o0, o0 + nc) of the map, rows and tiles of the chunk
     std::vector<int> base;                      // per object of the chunk: chunk row of its first candidate (negative: the chunk starts inside it)
     std::vector<int4> tiles;                    // {first row, count, code-bias slot, 0}
+    std::vector<int> slot_obj;                  // the object of each code-bias slot: the chunk's objects that have rows in it, ascending
     std::vector<float> cb;                      // code biases of the objects that have rows in the chunk, in slot order
 };
 
-// the chunks of one pass from the objects' candidate counts: consecutive objects, or a range of one object's candidates, of at most `budget` rows
-std::vector<QueryChunk> query_plan(const dsp_handle* h, const float* codes, const std::vector<int>& cnt, int64_t budget) {
+// points of one pass: QUERY_PASS_PTS, and fewer (whole waves) where n_obj x waves counts would exceed QUERY_WAVECNT_BYTES.  1 <= n_obj <= QUERY_MAX_OBJ
+int64_t query_pass_pts(int64_t n_obj) {
+    return std::min<int64_t>(QUERY_PASS_PTS, (int64_t)(QUERY_WAVECNT_BYTES / sizeof(int) / (size_t)n_obj) * 64);
+}
+
+int64_t query_default_budget() { return (int64_t)(QUERY_CHUNK_BYTES / (GRAD_STRIDE * sizeof(float))); }
+
+// The chunks of one pass from the objects' candidate counts: consecutive objects, or a range of one object's candidates, of at most `budget`
+// rows.  Geometry only -- a function of (cnt, budget), no handle and no device (dsp_debug_query_plan); query_plan_codes fills cb.
+std::vector<QueryChunk> query_plan_geometry(const int* cnt, int64_t n_obj, int64_t budget) {
     std::vector<QueryChunk> plan;
-    const int64_t n_obj = (int64_t)cnt.size();
     int64_t o = 0, used = 0;                    // the next candidate without a chunk: candidate `used` of object o
     for (;;) {
         while (o < n_obj && used >= cnt[o]) { ++o; used = 0; }
@@ -55,8 +64,7 @@ std::vector<QueryChunk> query_plan(const dsp_handle* h, const float* codes, cons
             c.base.push_back((int)(rows - used));
             if (take > 0) {
                 for (int64_t i = 0; i < take; i += TILE_PTS) c.tiles.push_back(make_int4((int)(rows + i), (int)std::min<int64_t>(TILE_PTS, take - i), slot, 0));
-                c.cb.resize((size_t)(slot + 1) * 2 * WIDTH);
-                code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + o * CODE_LEN, c.cb.data() + (size_t)slot * 2 * WIDTH);
+                c.slot_obj.push_back((int)o);
                 ++slot;
             }
             rows += take;
@@ -69,6 +77,21 @@ std::vector<QueryChunk> query_plan(const dsp_handle* h, const float* codes, cons
         c.n_rows = (int)rows;
         c.nt = (int)c.tiles.size();
     }
+    return plan;
+}
+
+// the code biases of every chunk's slots
+void query_plan_codes(const dsp_handle* h, const float* codes, std::vector<QueryChunk>& plan) {
+    for (QueryChunk& c : plan) {
+        c.cb.resize(c.slot_obj.size() * 2 * WIDTH);
+        for (size_t slot = 0; slot < c.slot_obj.size(); ++slot)
+            code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + (size_t)c.slot_obj[slot] * CODE_LEN, c.cb.data() + slot * 2 * WIDTH);
+    }
+}
+
+std::vector<QueryChunk> query_plan(const dsp_handle* h, const float* codes, const std::vector<int>& cnt, int64_t budget) {
+    std::vector<QueryChunk> plan = query_plan_geometry(cnt.data(), (int64_t)cnt.size(), budget);
+    query_plan_codes(h, codes, plan);
     return plan;
 }
 
@@ -118,8 +141,8 @@ struct QueryDev {
 // chunks, passes}.  n_pts > 0, n_obj > 0.
 void query_core(dsp_handle* h, const float* codes, int64_t n_obj, int64_t n_pts, const QueryDev& d, bool jacobian, std::vector<QueryChunk>& plan,
                 QueryTimer& timer, int64_t* stats4, const std::function<void(const QueryChunk&)>& behind_reduce) {
-    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : (int64_t)(QUERY_CHUNK_BYTES / (GRAD_STRIDE * sizeof(float)));
-    const int64_t pass_pts = std::min<int64_t>(QUERY_PASS_PTS, (int64_t)(QUERY_WAVECNT_BYTES / sizeof(int) / (size_t)n_obj) * 64);
+    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : query_default_budget();
+    const int64_t pass_pts = query_pass_pts(n_obj);
     std::vector<int> cnt((size_t)n_obj);
     h->q_cnt.ensure((size_t)n_obj);
     h->s_ntiles.ensure(1);
@@ -521,6 +544,32 @@ int dsp_debug_query_select(int64_t n_rows, const float* sdf, const float* scale_
     for (int64_t r = 0; r < n_rows; ++r)
         if (pt_of_row[r] < 0 || pt_of_row[r] >= n_pts || obj_of_row[r] < 0) return DSP_E_ARG;
     query_select_host(n_rows, sdf, scale_of_row, obj_of_row, pt_of_row, n_pts, obj, dist);
+    return DSP_OK;
+}
+
+int dsp_debug_query_plan(int64_t n_obj, const int32_t* cnt, int64_t budget, int64_t pass_n_obj, int64_t* sizes3, int32_t* chunks4, int32_t* base,
+                         int32_t* tiles4, int64_t* pass_pts) {
+    if (n_obj < 0 || n_obj > QUERY_MAX_OBJ || (n_obj > 0 && !cnt) || budget < 0 || budget > ((int64_t)1 << 24)) return DSP_E_ARG;
+    if (pass_pts && (pass_n_obj < 1 || pass_n_obj > QUERY_MAX_OBJ)) return DSP_E_ARG;
+    for (int64_t o = 0; o < n_obj; ++o)
+        if (cnt[o] < 0) return DSP_E_ARG;
+    if (pass_pts) *pass_pts = query_pass_pts(pass_n_obj);
+    if (!sizes3 && !chunks4 && !base && !tiles4) return DSP_OK;
+    std::vector<QueryChunk> plan;
+    try {
+        plan = query_plan_geometry(cnt, n_obj, budget > 0 ? budget : query_default_budget());
+    } catch (const std::bad_alloc&) {
+        return DSP_E_NOMEM;
+    }
+    int64_t nb = 0, nt = 0;
+    for (const QueryChunk& c : plan) {
+        if (chunks4) { chunks4[0] = c.o0; chunks4[1] = c.nc; chunks4[2] = c.n_rows; chunks4[3] = c.nt; chunks4 += 4; }
+        if (base) memcpy(base + nb, c.base.data(), c.base.size() * sizeof(int));
+        if (tiles4) memcpy(tiles4 + 4 * nt, c.tiles.data(), c.tiles.size() * sizeof(int4));
+        nb += (int64_t)c.base.size();
+        nt += (int64_t)c.tiles.size();
+    }
+    if (sizes3) { sizes3[0] = (int64_t)plan.size(); sizes3[1] = nb; sizes3[2] = nt; }
     return DSP_OK;
 }
 

@@ -338,6 +338,16 @@ int dsp_debug_query_select(int64_t n_rows, const float* sdf, const float* scale_
 /* Testing: this handle's chunk budget of the map query in decoder rows (0 = the default, 64 MiB of rows), so that a small call crosses
  * chunk borders. */
 int dsp_debug_query_chunk_rows(dsp_handle* h, int64_t rows);
+/* Host only, no handle: how dsp_map_query cuts one pass into chunks, as a function of the objects' candidate counts (cnt, n_obj entries
+ * >= 0, in object order) and the chunk budget in rows (0 = the default; at most 2^24).  A chunk holds consecutive rows of the list of all
+ * (object, candidate) pairs in order: chunks4 receives {o0, nc, n_rows, nt} per chunk (objects [o0, o0 + nc), rows, tiles); base, nc
+ * entries per chunk concatenated: chunk row base[k] + j holds candidate j of object o0 + k (negative: the chunk starts inside the object;
+ * only rows inside [0, n_rows) belong to the chunk); tiles4, nt x 4 per chunk concatenated: {first row, rows (1 .. 64, of one object),
+ * code-bias slot, 0}, slots counting the chunk's objects that have rows in it.  sizes3 = {chunks, entries of base, tiles}; a call with the
+ * three arrays NULL only sizes.  pass_pts (optional) receives the points of one pass of a map of pass_n_obj objects (1 .. 2^18): 131 072,
+ * fewer from 8193 objects on.  DSP_E_ARG: a negative count, a budget or object count out of range. */
+int dsp_debug_query_plan(int64_t n_obj, const int32_t* cnt, int64_t budget, int64_t pass_n_obj, int64_t* sizes3, int32_t* chunks4, int32_t* base,
+                         int32_t* tiles4, int64_t* pass_pts);
 /* Measurement: on != 0 brackets the following dsp_map_query calls on this handle, and every decoder launch inside them, with HIP events on
  * the handle's stream; ms2 (optional) receives {decoder launches, whole call} of the last such call in milliseconds (0, 0 before one).
  * The results of a call do not depend on it. */

@@ -133,6 +133,60 @@ def normals(rt, g):
     return np.where(flat[:, None], F32(0), n).astype(F32)
 
 
+def plan(cnt, budget):
+    """How dsp_map_query cuts one pass into chunks, stated plainly: the list of all (object, candidate) pairs in order -- object 0's
+    candidates 0, 1, ..., then object 1's -- cut every `budget` rows.  -> pairs (n_rows_total, 2) int64; chunk c holds
+    pairs[c * budget:(c + 1) * budget], its row r is pairs[c * budget + r]."""
+    cnt = np.asarray(cnt, np.int64)
+    ob = np.repeat(np.arange(cnt.size, dtype=np.int64), cnt)
+    first = np.cumsum(cnt) - cnt
+    return np.stack([ob, np.arange(ob.size, dtype=np.int64) - first[ob]], 1)
+
+
+TAU_DEC = 5e-6          # |fp32 decoder - float64 oracle|, the bound tests/test_gpu_decoders.py asserts
+
+
+def expected64(dec, t_world_obj, codes, pts, ref):
+    """The map query in plain float64, nothing restated from query_math.h: p_o = T^-1 p (numpy.linalg.inv of the float32 pose taken
+    exactly), s = det(T[:3, :3]) ** (1 / 3), dist = s * sdf64(code, p_o) by the float64 oracle decoder `dec`, the normal R g / |g| with
+    R = T[:3, :3] / s, the bound min over objects of (|p_o| - 1) s.  Only WHICH (object, point) pairs are decoded and which objects enter
+    the bound is taken from the restatement `ref` (expected(...)): a point within rounding of a sphere's border is a candidate for one and
+    not for the other, and that border is pinned bit for bit by tests/test_query_host.py.
+
+    -> dict over the restatement's candidate rows (object-major, ascending points: ref["rows"]): obj, pt, d (s * sdf64), g (d sdf / d xyz,
+    object frame), g_flip (the same with every ReLU within fp32 round-off of its kink on its other side; the round-off includes the
+    point's own |p_o32 - p_o64|), n (world unit normal of g), delta (|p_o32 - p_o64|), tol (s (TAU_DEC + 2 |g| delta)); and per point
+    bound, bound_tol (see tests/test_gpu_map_scale.py::test_large_map_against_float64)."""
+    from oracle import dsp_oracle as O
+    t = np.asarray(t_world_obj, F32).reshape(-1, 4, 4).astype(np.float64)
+    p = np.asarray(pts, F32).reshape(-1, 3).astype(np.float64)
+    inv = np.linalg.inv(t)
+    s = np.cbrt(np.linalg.det(t[:, :3, :3]))
+    ob, pt = ref["rows"]["obj"].astype(np.int64), ref["rows"]["pt"].astype(np.int64)
+    p_o = np.einsum("nij,nj->ni", inv[ob, :3, :3], p[pt]) + inv[ob, :3, 3]
+    dp = np.abs(ref["p_obj"][ob, pt].astype(np.float64) - p_o)
+    delta = np.sqrt((dp * dp).sum(1))
+    code = np.stack([np.asarray(c, F32)[:dec.code_len] for c in codes]).astype(np.float64)
+    y, g, g_flip = O._decoder_fb64(dec, np.concatenate([code[ob], p_o], 1), True, dp)      # ONE call over all rows, each with its own code
+    g, g_flip = g[:, -3:], g_flip[:, -3:]
+    gn = np.sqrt((g * g).sum(1))
+    rot = t[:, :3, :3] / s[:, None, None]
+    n = np.einsum("nij,nj->ni", rot[ob], g) / gn[:, None]
+    # the bound, dense: every object whose sphere the restatement puts the point outside of
+    outside = ~ref["inside"]
+    po_all = np.einsum("oij,pj->opi", inv[:, :3, :3], p) + inv[:, None, :3, 3]
+    b_all = np.where(outside, (np.sqrt((po_all * po_all).sum(2)) - 1.0) * s[:, None], np.inf)
+    eps32 = float(np.finfo(F32).eps)
+    t_ow = np.sqrt((inv[:, :3, 3] ** 2).sum(1))
+    tol_all = 4.0 * eps32 * (t_ow[:, None] + np.sqrt((p * p).sum(1))[None, :] / s[:, None]) * s[:, None]
+    bound = b_all.min(0)
+    # the fp32 minimum may sit at another object than the float64 one: any object within twice the largest tolerance of the minimum
+    near = b_all <= bound[None, :] + 2.0 * tol_all.max(0)[None, :]
+    bound_tol = np.where(near, tol_all, 0.0).max(0)
+    return {"obj": ob, "pt": pt, "d": s[ob] * y, "g": g, "g_flip": g_flip, "n": n, "delta": delta, "scale": s,
+            "tol": s[ob] * (TAU_DEC + 2.0 * gn * delta), "bound": bound, "bound_tol": bound_tol}
+
+
 def random_rotations(rng, n):
     """uniform rotations (n, 3, 3) float64 from unit quaternions."""
     q = rng.normal(size=(n, 4))

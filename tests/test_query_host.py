@@ -20,7 +20,7 @@ from dsp_slam_amd import map_objects as M
 
 F32 = np.float32
 NEW = ["dsp_map_query", "dsp_map_query_last_stats", "dsp_debug_query_invert", "dsp_debug_query_candidates", "dsp_debug_query_select",
-       "dsp_debug_query_chunk_rows"]
+       "dsp_debug_query_chunk_rows", "dsp_debug_query_plan"]
 E_ARG = -1
 
 

@@ -22,6 +22,8 @@ OBJ_GOOD, OBJ_FEW_SAMPLES, OBJ_NAN = 0, 1, 2
 PREPASS_OFF, PREPASS_F16, PREPASS_BF16 = 0, 1, 2
 MESH_REGULAR_GRID, MESH_PREPASS_F16, MESH_PREPASS_BF16 = 1, 2, 4     # dsp_extract_mesh(es) flags
 QUERY_NORMALS = 1                                                    # dsp_map_query flags
+RAYCAST_NORMALS = 1                                                  # dsp_map_raycast flags
+RAYCAST_MISS, RAYCAST_HIT, RAYCAST_UNDECIDED = 0, 1, 2               # ... a ray's status
 ALIGN_OK, ALIGN_CONVERGED, ALIGN_NO_SUPPORT, ALIGN_SINGULAR = 0, 1, 2, 3      # dsp_map_align: a hypothesis' status
 ALIGN_RECORD, ALIGN_TRACE = 50, 53                                   # ... doubles per record / per traced evaluation
 PREPASS_SMALL_TILES = 0x100
@@ -51,6 +53,10 @@ class AlignParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("min_points", C.c_int32), ("max_dist", C.c_double), ("huber", C.c_double), ("damp", C.c_double),
                 ("trans_tol", C.c_double), ("rot_tol", C.c_double),
                 ("lambda0", C.c_double), ("up", C.c_double), ("down", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
+class RaycastParams(C.Structure):
+    _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("eps", C.c_float), ("relax", C.c_float), ("max_steps", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -168,6 +174,14 @@ SYMBOLS = [
     ("dsp_debug_query_chunk_rows", C.c_int, [_VP, C.c_int64]),
     ("dsp_debug_query_plan", C.c_int, [C.c_int64, c_i32p, C.c_int64, C.c_int64, c_i64p, c_i32p, c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_query_timing", C.c_int, [_VP, C.c_int, c_f64p]),
+    ("dsp_raycast_params_default", None, [C.POINTER(RaycastParams)]),
+    ("dsp_map_raycast", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.POINTER(RaycastParams), C.c_int32, c_i32p, c_f32p, c_f32p,
+                                  c_i32p, c_f32p]),
+    ("dsp_map_raycast_last_stats", C.c_int, [_VP, c_i64p]),
+    ("dsp_debug_raycast_check", C.c_int, [C.POINTER(RaycastParams)]),
+    ("dsp_debug_raycast_segments", C.c_int, [C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_float, C.c_float, C.POINTER(C.c_uint8),
+                                             C.POINTER(C.c_uint8), c_f32p, c_f32p, c_f32p, c_f32p]),
+    ("dsp_debug_raycast_step", C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(RaycastParams), c_i32p, c_f32p, c_f32p]),
     ("dsp_align_params_default", None, [C.POINTER(AlignParams)]),
     ("dsp_map_align", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f64p, C.c_int64, C.POINTER(AlignParams), c_f64p, c_f64p,
                                 c_i32p, c_f32p, c_f64p]),

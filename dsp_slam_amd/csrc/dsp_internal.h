@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "prior_math.h"
+#include "raycast_math.h"
 #include "step_rule.h"
 
 namespace dsp {
@@ -546,6 +547,64 @@ void query_candidates_host(int64_t n_obj, const float* rt, const float* scale, i
                            float* bound);
 void query_select_host(int64_t n_rows, const float* sdf, const float* scale_of_row, const int32_t* obj_of_row, const int32_t* pt_of_row, int64_t n_pts,
                        int32_t* obj, float* dist);
+
+// ---- ray casting against the map (raycast_kernels.hip; the arithmetic: raycast_math.h) ------------
+// The device arrays of one call: n_rays world rays (packed float3 origins and directions) and the object table in; per ray the hit key
+// (orderable(t_hit) << 32 | obj), the smallest parameter of its exhausted pairs (orderable bits, all ones = none) and the outputs.
+// dstats = {decoder rows, tiles, rounds that decoded a row, exhausted pairs} of the march, kept on the device.
+struct RaycastDev {
+    const float *org, *dir, *tab;
+    int n_rays, n_obj, n_waves;         // n_waves = ceil(n_rays / 64)
+    raycast_math::Params prm;
+    unsigned long long* best;
+    unsigned* exh;
+    int* obj;
+    float *t, *dist;
+    int* status;
+    float* normal;                      // null: no normals
+    unsigned long long* dstats;
+};
+// One pass: the pairs [lo, hi) of each of the objects [o0, o0 + nc), held in n_slots slots (a multiple of 64; every object's pairs start at
+// a multiple of 64).  The host uploads, once per pass: pobj[k] = {slot offset added to the pair index, lo, hi, 0}; ob[k] = {first wave of
+// slots, waves, object index, 0}; wtab[wave] = {object of the pass, the object's first wave}.  Everything else is written on the device:
+// the pair state (pr_*), and per round live_cnt / wave_row per wave of slots, oinfo per object, ctrl = {tiles, live rows}, the compacted
+// samples pts4 with row_slot, and the tile list.
+struct RaycastPass {
+    int o0, nc, n_slots;
+    const int4* pobj;
+    const int4* ob;
+    const int2* wtab;
+    int2* pr_meta;                      // {ray, object}
+    int* pr_state;                      // 0 live, 1 hit, 2 ended as a miss, anything else padding
+    float *pr_t, *pr_t1, *pr_dist;
+    float4 *pr_oo, *pr_do;
+    int *live_cnt, *wave_row;
+    int4* oinfo;
+    int* ctrl;
+    float4* pts4;
+    int* row_slot;
+    int4* tiles;
+};
+// count: wave_cnt[n_obj][n_waves] <- existing pairs per (object, wave) and its scan, cnt[obj]; best / exh / dist initialised for every ray.
+// fill: the pass's pair state.  round_front: retirement and live counts, the scan (ONE block), the compacted samples and the tile list.
+// step: the step rule on the decoder's values sdf[row].  end: the pass's exhausted pairs and the winners' dist.  finish: obj, t, status.
+// wincount / winfill / normal: the winners grouped by object in ascending ray order, their hit samples, their world normals.
+hipError_t launch_raycast_count(const RaycastDev& d, int* wave_cnt, int* cnt, hipStream_t s);
+hipError_t launch_raycast_fill(const RaycastDev& d, const RaycastPass& p, const int* wave_base, hipStream_t s);
+hipError_t launch_raycast_round_front(const RaycastDev& d, const RaycastPass& p, hipStream_t s);
+hipError_t launch_raycast_step(const RaycastDev& d, const RaycastPass& p, const float* sdf, hipStream_t s);
+hipError_t launch_raycast_end(const RaycastDev& d, const RaycastPass& p, hipStream_t s);
+hipError_t launch_raycast_finish(const RaycastDev& d, hipStream_t s);
+hipError_t launch_raycast_wincount(const RaycastDev& d, int* wave_cnt, int* cnt, hipStream_t s);
+hipError_t launch_raycast_winfill(const RaycastDev& d, int o0, int nc, const int* base, const int* wave_base, int n_rows, float4* pts4, int2* row_meta,
+                                  hipStream_t s);
+hipError_t launch_raycast_normal(const RaycastDev& d, const float* rows, const int2* row_meta, int n_rows, hipStream_t s);
+// raycast_math.h compiled for the host in the translation unit that has contraction off (dsp_debug_raycast_*)
+void raycast_segments_host(int64_t n_obj, const float* rt, const float* scale, int64_t n_rays, const float* org, const float* dir, float t_min, float t_max,
+                           unsigned char* is_void, unsigned char* exists, float* t0, float* t1, float* o_o, float* d_o);
+void raycast_step_host(int64_t n, const float* t, const float* t1, const float* sdf, const float* s, float eps, float relax, int32_t* decision,
+                       float* dist, float* t_next);
+const char* raycast_check_host(float t_min, float t_max, float eps, float relax, int max_steps);
 
 // ---- map alignment (align_kernels.hip; the arithmetic: align_math.h) ----------------------------
 // hyp: ALIGN_HYP_STRIDE floats per hypothesis {[R | t] of the sensor-to-world pose in fp32, 12; live (1 / 0); 0, 0, 0}.  Rows are

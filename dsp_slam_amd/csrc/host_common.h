@@ -260,6 +260,8 @@ struct dsp_handle {
     double q_ms[2] = {0.0, 0.0};            // ... {decoder launches, whole call} of the last call, ms on the handle's stream
     // map alignment (align_run) runs the query's core on the scratch above; the last call's stats
     int64_t a_stats[5] = {0, 0, 0, 0, 0};   // candidate rows, decoder tiles, chunks, point passes, evaluations
+    // ray casting (raycast_run) holds its arrays as blocks of the pool for the length of the call and shares q_chunk_rows; the last call's stats
+    int64_t r_stats[6] = {0, 0, 0, 0, 0, 0};    // pairs, decoder rows, tiles, rounds run, passes, exhausted pairs
     // dsp_mesh_last_stats: prepass points, fp32 band points, fp32 audit points, points decoded densely in fp32, objects re-run dense;
     // largest guard error
     int64_t ms_counts[5] = {0, 0, 0, 0, 0};

@@ -265,6 +265,206 @@ std::vector<float> query_table(const dsp_handle* h, const float* t_world_obj, co
 }
 
 // ------------------------------------------------------------------------------------------------
+// ray casting (dsp_map_raycast; arithmetic: raycast_math.h, kernels: raycast_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// The code biases of ALL objects of a call live in one device table (4 KiB per object) of at most RAYCAST_CBIAS_BYTES: 16 384 objects.  The
+// pair counts per (object, wave of rays) share the query's budget QUERY_WAVECNT_BYTES.  Both fixed, whatever the device has free.
+constexpr size_t RAYCAST_CBIAS_BYTES = (size_t)64 << 20;
+constexpr int RAYCAST_POLL_ROUNDS = 8;      // the host reads the live count back every so many rounds to stop enqueueing early
+
+// what one pass uploads (RaycastPass, dsp_internal.h); kept until the stream has been synchronised behind the pass's launches
+struct RaycastPassHost {
+    int o0 = 0, nc = 0, n_slots = 0;
+    std::vector<int4> pobj, ob;
+    std::vector<int2> wtab;
+};
+
+// The passes of a call from the objects' pair counts: the chunks of query_plan_geometry -- consecutive objects, or a range of one object's
+// pairs, of at most `budget` pairs -- with every object's pairs padded to whole waves of slots.
+std::vector<RaycastPassHost> raycast_passes(const int* cnt, int64_t n_obj, int64_t budget) {
+    std::vector<RaycastPassHost> passes;
+    for (const QueryChunk& c : query_plan_geometry(cnt, n_obj, budget)) {
+        passes.emplace_back();
+        RaycastPassHost& p = passes.back();
+        p.o0 = c.o0;
+        p.nc = c.nc;
+        int slots = 0;
+        for (int k = 0; k < c.nc; ++k) {
+            const int lo = std::max(0, -c.base[k]);
+            const int hi = std::max(lo, (int)std::min<int64_t>(cnt[c.o0 + k], (int64_t)c.n_rows - c.base[k]));
+            const int waves = (hi - lo + 63) / 64;
+            p.pobj.push_back(make_int4(slots - lo, lo, hi, 0));
+            p.ob.push_back(make_int4(slots / 64, waves, c.o0 + k, 0));
+            for (int w = 0; w < waves; ++w) p.wtab.push_back(make_int2(k, slots / 64));
+            slots += waves * 64;
+        }
+        p.n_slots = slots;
+    }
+    return passes;
+}
+
+void raycast_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* org, const float* dir, int64_t n_rays,
+                 const raycast_math::Params& prm, int32_t* obj, float* t, float* dist, int32_t* status, float* normal) {
+    for (auto& c : h->r_stats) c = 0;
+    if (n_rays == 0) return;
+    if (n_obj == 0) {
+        for (int64_t i = 0; i < n_rays; ++i) {
+            obj[i] = -1;
+            t[i] = dist[i] = INFINITY;
+            status[i] = raycast_math::STATUS_MISS;
+            if (normal) normal[3 * i] = normal[3 * i + 1] = normal[3 * i + 2] = 0.f;
+        }
+        return;
+    }
+    const int64_t n_waves = (n_rays + 63) / 64;
+    if ((size_t)n_obj * 2 * WIDTH * sizeof(float) > RAYCAST_CBIAS_BYTES || (size_t)n_obj * (size_t)n_waves * sizeof(int) > QUERY_WAVECNT_BYTES)
+        throw std::invalid_argument("raycast: objects x rays too large (split the request)");
+    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : query_default_budget();
+    HIP_TRY(hipSetDevice(h->device));
+    DevBuf<float> r_org, r_dir, r_tab, r_t, r_dist, r_normal, r_cb, p_t, p_t1, p_dist, p_out, n_out;
+    DevBuf<unsigned long long> r_best, r_dstats;
+    DevBuf<unsigned> r_exh;
+    DevBuf<int> r_obj, r_status, r_wave_cnt, r_cnt, p_state, p_live, p_wrow, p_ctrl, p_rslot, n_base, n_ntiles;
+    DevBuf<int2> p_wtab, p_meta, n_meta;
+    DevBuf<int4> p_pobj, p_ob, p_oinfo, p_tiles, n_tiles;
+    DevBuf<float4> p_oo, p_do, p_pts, n_pts;
+    std::vector<int> cnt((size_t)n_obj);
+    std::vector<float> cb((size_t)n_obj * 2 * WIDTH);
+    std::vector<RaycastPassHost> passes;        // the uploads of the passes in flight are copied from here ...
+    std::vector<QueryChunk> plan;               // ... and those of the normals' chunks from here
+    unsigned long long dstats[4] = {0, 0, 0, 0};
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    for (int64_t o = 0; o < n_obj; ++o) code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + (size_t)o * CODE_LEN, cb.data() + (size_t)o * 2 * WIDTH);
+    r_org.alloc((size_t)n_rays * 3);
+    r_dir.alloc((size_t)n_rays * 3);
+    r_tab.alloc(tab.size());
+    r_cb.alloc(cb.size());
+    r_best.alloc((size_t)n_rays);
+    r_exh.alloc((size_t)n_rays);
+    r_obj.alloc((size_t)n_rays);
+    r_t.alloc((size_t)n_rays);
+    r_dist.alloc((size_t)n_rays);
+    r_status.alloc((size_t)n_rays);
+    if (normal) r_normal.alloc((size_t)n_rays * 3);
+    r_dstats.alloc(4);
+    r_wave_cnt.alloc((size_t)n_obj * n_waves);
+    r_cnt.alloc((size_t)n_obj);
+    h->s_clk.ensure(4);
+    HIP_TRY(hipMemcpyAsync(r_org.p, org, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(r_dir.p, dir, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(r_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(r_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(r_dstats.p, 0, sizeof dstats, h->stream));
+    const RaycastDev d{r_org.p, r_dir.p, r_tab.p, (int)n_rays, (int)n_obj, (int)n_waves, prm, r_best.p, r_exh.p, r_obj.p, r_t.p, r_dist.p, r_status.p,
+                       normal ? r_normal.p : nullptr, r_dstats.p};
+    HIP_TRY(launch_raycast_count(d, r_wave_cnt.p, r_cnt.p, h->stream));
+    HIP_TRY(hipMemcpyAsync(cnt.data(), r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));           // the pair counts, once per call
+    passes = raycast_passes(cnt.data(), n_obj, budget);
+    for (int c : cnt) h->r_stats[0] += c;
+    h->r_stats[4] = (int64_t)passes.size();
+    size_t max_slots = 0, max_nc = 0;
+    for (const RaycastPassHost& p : passes) { max_slots = std::max<size_t>(max_slots, p.n_slots); max_nc = std::max<size_t>(max_nc, p.nc); }
+    if (!passes.empty()) {
+        p_pobj.alloc(max_nc); p_ob.alloc(max_nc); p_oinfo.alloc(max_nc);
+        p_wtab.alloc(max_slots / 64); p_live.alloc(max_slots / 64); p_wrow.alloc(max_slots / 64); p_tiles.alloc(max_slots / 64);
+        p_meta.alloc(max_slots); p_state.alloc(max_slots); p_t.alloc(max_slots); p_t1.alloc(max_slots); p_dist.alloc(max_slots);
+        p_oo.alloc(max_slots); p_do.alloc(max_slots); p_pts.alloc(max_slots); p_rslot.alloc(max_slots); p_out.alloc(max_slots);
+        p_ctrl.alloc(2);
+    }
+    for (const RaycastPassHost& ph : passes) {
+        if (ph.n_slots <= 0) continue;
+        const RaycastPass p{ph.o0, ph.nc, ph.n_slots, p_pobj.p, p_ob.p, p_wtab.p, p_meta.p, p_state.p, p_t.p, p_t1.p, p_dist.p, p_oo.p, p_do.p,
+                            p_live.p, p_wrow.p, p_oinfo.p, p_ctrl.p, p_pts.p, p_rslot.p, p_tiles.p};
+        HIP_TRY(hipMemcpyAsync(p_pobj.p, ph.pobj.data(), ph.pobj.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(p_ob.p, ph.ob.data(), ph.ob.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(p_wtab.p, ph.wtab.data(), ph.wtab.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemsetAsync(p_state.p, 0xff, (size_t)ph.n_slots * sizeof(int), h->stream));         // padding: neither live nor hit
+        HIP_TRY(hipMemsetAsync(p_meta.p, 0xff, (size_t)ph.n_slots * sizeof(int2), h->stream));
+        HIP_TRY(launch_raycast_fill(d, p, r_wave_cnt.p, h->stream));
+        MlpArgs a = make_mlp_args(h, 0);
+        a.n_tiles = p_ctrl.p;
+        a.tiles = p_tiles.p;
+        a.pts = p_pts.p;
+        a.code_bias = r_cb.p;
+        a.code_bias_stride = 2 * WIDTH;
+        a.out_sdf = p_out.p;
+        a.out_grad = p_out.p;
+        a.clk = h->s_clk.p;
+        const int grid = std::min(ph.n_slots / 64, h->n_cu);
+        for (int round = 0; round < prm.max_steps; ++round) {
+            HIP_TRY(launch_raycast_round_front(d, p, h->stream));
+            timer.mark();
+            HIP_TRY(launch_mlp(0, a, grid, h->stream));
+            timer.mark();
+            HIP_TRY(launch_raycast_step(d, p, p_out.p, h->stream));
+            if ((round + 1) % RAYCAST_POLL_ROUNDS == 0 && round + 1 < prm.max_steps) {
+                int live = 0;
+                HIP_TRY(hipMemcpyAsync(&live, p_ctrl.p + 1, sizeof live, hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                if (live == 0) break;           // the round just run decoded nothing: no later one would
+            }
+        }
+        HIP_TRY(launch_raycast_end(d, p, h->stream));
+    }
+    HIP_TRY(launch_raycast_finish(d, h->stream));
+    if (normal) {       // the winners' hit samples through the jacobian form, grouped by object in ascending ray order
+        HIP_TRY(launch_raycast_wincount(d, r_wave_cnt.p, r_cnt.p, h->stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        plan = query_plan_geometry(cnt.data(), n_obj, budget);
+        size_t max_rows = 0, max_nt = 0, max_base = 0;
+        for (QueryChunk& c : plan) {
+            for (int4& tile : c.tiles) tile.z = c.slot_obj[tile.z];        // the slot of the call's code-bias table: the object itself
+            max_rows = std::max<size_t>(max_rows, c.n_rows); max_nt = std::max<size_t>(max_nt, c.nt); max_base = std::max<size_t>(max_base, c.nc);
+        }
+        if (!plan.empty()) {
+            n_pts.alloc(max_rows); n_out.alloc(max_rows * GRAD_STRIDE); n_meta.alloc(max_rows); n_tiles.alloc(max_nt); n_base.alloc(max_base);
+            n_ntiles.alloc(1);
+        }
+        for (const QueryChunk& c : plan) {
+            HIP_TRY(hipMemcpyAsync(n_tiles.p, c.tiles.data(), c.nt * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(n_ntiles.p, &c.nt, 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(n_base.p, c.base.data(), c.nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(launch_raycast_winfill(d, c.o0, c.nc, n_base.p, r_wave_cnt.p, c.n_rows, n_pts.p, n_meta.p, h->stream));
+            MlpArgs a = make_mlp_args(h, 2);
+            a.n_tiles = n_ntiles.p;
+            a.tiles = n_tiles.p;
+            a.pts = n_pts.p;
+            a.code_bias = r_cb.p;
+            a.code_bias_stride = 2 * WIDTH;
+            a.out_sdf = n_out.p;
+            a.out_grad = n_out.p;
+            a.clk = h->s_clk.p;
+            timer.mark();
+            HIP_TRY(launch_mlp(2, a, std::min(c.nt, h->n_cu), h->stream));
+            timer.mark();
+            HIP_TRY(launch_raycast_normal(d, n_out.p, n_meta.p, c.n_rows, h->stream));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(obj, r_obj.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(t, r_t.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dist, r_dist.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(status, r_status.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    if (normal) HIP_TRY(hipMemcpyAsync(normal, r_normal.p, (size_t)n_rays * 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dstats, r_dstats.p, sizeof dstats, hipMemcpyDeviceToHost, h->stream));
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));           // `passes` and `plan` (the uploads) live until here
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+    h->r_stats[1] = (int64_t)dstats[0];
+    h->r_stats[2] = (int64_t)dstats[1];
+    h->r_stats[3] = (int64_t)dstats[2];
+    h->r_stats[5] = (int64_t)dstats[3];
+}
+
+raycast_math::Params raycast_params(const dsp_raycast_params& p) { return raycast_math::Params{p.t_min, p.t_max, p.eps, p.relax, p.max_steps}; }
+
+// ------------------------------------------------------------------------------------------------
 // map alignment (dsp_map_align; arithmetic: align_math.h, kernels: align_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 
@@ -465,6 +665,53 @@ int dsp_map_query(dsp_handle* h, const float* t_world_obj, const float* codes, i
         const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
         query_run(h, tab, codes, n_obj, pts_world, n_pts, obj, dist, bound, normal);
     });
+}
+
+void dsp_raycast_params_default(dsp_raycast_params* p) {
+    if (!p) return;
+    *p = dsp_raycast_params{raycast_math::DEFAULT_T_MIN, INFINITY, raycast_math::DEFAULT_EPS, raycast_math::DEFAULT_RELAX, raycast_math::DEFAULT_MAX_STEPS};
+}
+
+int dsp_map_raycast(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* origins, const float* dirs, int64_t n_rays,
+                    const dsp_raycast_params* params, int32_t flags, int32_t* obj, float* t, float* dist, int32_t* status, float* normal) {
+    if (!h || !params || n_obj < 0 || n_rays < 0 || (flags & ~DSP_RAYCAST_NORMALS)) return DSP_E_ARG;
+    const bool normals = (flags & DSP_RAYCAST_NORMALS) != 0;
+    if ((n_obj > 0 && (!t_world_obj || !codes)) || (!normals && normal)) return DSP_E_ARG;
+    if (n_rays > 0 && (!origins || !dirs || !obj || !t || !dist || !status || (normals && !normal))) return DSP_E_ARG;
+    return guarded(h, [&] {
+        const raycast_math::Params prm = raycast_params(*params);
+        if (const char* why = raycast_check_host(prm.t_min, prm.t_max, prm.eps, prm.relax, prm.max_steps)) throw std::invalid_argument(why);
+        if (n_rays > (int64_t)0x7fffffff) throw std::invalid_argument("raycast too large (split the request)");
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        raycast_run(h, tab, codes, n_obj, origins, dirs, n_rays, prm, obj, t, dist, status, normal);
+    });
+}
+
+int dsp_map_raycast_last_stats(dsp_handle* h, int64_t* counts6) {
+    if (!h || !counts6) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts6, h->r_stats, sizeof h->r_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_raycast_check(const dsp_raycast_params* params) {
+    if (!params) return DSP_E_ARG;
+    return raycast_check_host(params->t_min, params->t_max, params->eps, params->relax, params->max_steps) ? DSP_E_ARG : DSP_OK;
+}
+
+int dsp_debug_raycast_segments(int64_t n_obj, const float* rt_ow, const float* scale, int64_t n_rays, const float* origins, const float* dirs, float t_min,
+                               float t_max, unsigned char* is_void, unsigned char* exists, float* t0, float* t1, float* o_o, float* d_o) {
+    if (n_obj < 0 || n_rays < 0 || (n_obj > 0 && (!rt_ow || !scale)) || (n_rays > 0 && (!origins || !dirs))) return DSP_E_ARG;
+    raycast_segments_host(n_obj, rt_ow, scale, n_rays, origins, dirs, t_min, t_max, is_void, exists, t0, t1, o_o, d_o);
+    return DSP_OK;
+}
+
+int dsp_debug_raycast_step(int64_t n, const float* t, const float* t1, const float* sdf, const float* s, const dsp_raycast_params* params,
+                           int32_t* decision, float* dist, float* t_next) {
+    if (n < 0 || !params || (n > 0 && (!t || !t1 || !sdf || !s || !decision || !dist || !t_next))) return DSP_E_ARG;
+    if (raycast_check_host(params->t_min, params->t_max, params->eps, params->relax, params->max_steps)) return DSP_E_ARG;
+    raycast_step_host(n, t, t1, sdf, s, params->eps, params->relax, decision, dist, t_next);
+    return DSP_OK;
 }
 
 void dsp_align_params_default(dsp_align_params* p) {

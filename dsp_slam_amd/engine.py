@@ -879,6 +879,49 @@ class Engine(object):
         L.check(L.load().dsp_map_query_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_query_last_stats")
         return {"rows": int(c[0]), "tiles": int(c[1]), "chunks": int(c[2]), "passes": int(c[3])}
 
+    # -- ray casting -------------------------------------------------------------------------------
+    @staticmethod
+    def raycast_params(**params):
+        """dsp_raycast_params: the library's defaults with `params` written over them.  Fields: t_min, t_max, eps, relax, max_steps."""
+        prm = L.RaycastParams()
+        L.load().dsp_raycast_params_default(C.byref(prm))
+        names = {n for n, _ in L.RaycastParams._fields_}
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("cast_rays: unknown parameter %r" % k)
+            setattr(prm, k, int(v) if k == "max_steps" else float(v))
+        return prm
+
+    def cast_rays(self, t_world_obj, codes, origins, dirs, normals=False, **params):
+        """What does the map look like from here?  The first object surface along every world ray (dsp_map_raycast).  The map as query_map
+        takes it; origins, dirs: (n_rays, 3), dirs of any non-zero length; params: see raycast_params.  A dict: `obj` (int32, -1 for no
+        hit), `t` (the hit's parameter in world units along the unit direction, +inf for none), `dist` (sdf * scale at the hit sample, +inf
+        for none), `status` (L.RAYCAST_MISS / _HIT / _UNDECIDED) and `normal` ((n_rays, 3) world unit normals with normals=True, else
+        None)."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        org = L.f32(np.asarray(origins, np.float32).reshape(-1, 3))
+        dr = L.f32(np.asarray(dirs, np.float32).reshape(-1, 3))
+        n = org.shape[0]
+        if dr.shape[0] != n:
+            raise ValueError("one direction per origin")
+        prm = self.raycast_params(**params)
+        out = {"obj": np.zeros(n, np.int32), "t": np.zeros(n, np.float32), "dist": np.zeros(n, np.float32), "status": np.zeros(n, np.int32),
+               "normal": np.zeros((n, 3), np.float32) if normals else None}
+        L.check(L.load().dsp_map_raycast(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(org), L.ptr(dr), n, C.byref(prm),
+                                         L.RAYCAST_NORMALS if normals else 0, L.ptr(out["obj"], L.c_i32p), L.ptr(out["t"]), L.ptr(out["dist"]),
+                                         L.ptr(out["status"], L.c_i32p), L.ptr(out["normal"])), self._h, "dsp_map_raycast")
+        return out
+
+    def raycast_stats(self):
+        """Counts of the last cast_rays on this engine (dsp_map_raycast_last_stats)."""
+        c = np.zeros(6, np.int64)
+        L.check(L.load().dsp_map_raycast_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_raycast_last_stats")
+        return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5])}
+
     # -- map alignment -----------------------------------------------------------------------------
     @staticmethod
     def align_params(**params):

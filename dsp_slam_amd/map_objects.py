@@ -64,6 +64,49 @@ def localise(engine, objects, pts_sensor, t_world_sensor0, weights=None, trace=F
     return with_ids(res, [o["id"] for o in objects])
 
 
+def cast_rays(engine, objects, origins, dirs, normals=False, **params):
+    """Engine.cast_rays on the list read_map_objects returns: the first object surface along every world ray.  The result dict of
+    Engine.cast_rays (obj, t, dist, status, normal) plus `id`: the map's object id per ray, -1 where obj is -1."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    res = engine.cast_rays(poses, [o["code"] for o in objects], origins, dirs, normals=normals, **params)
+    return with_ids(res, [o["id"] for o in objects])
+
+
+def pixel_rays(K, t_world_cam, width, height):
+    """One world ray per pixel centre, row-major ((height * width, 3) float32 origins and directions) and cos ((height * width,) float64,
+    the cosine between each ray and the optical axis).  Pixel convention: integer pixel coordinates ARE the pixel centres (OpenCV's): the
+    pixel in column j and row i looks along K^-1 (j, i, 1) = ((j - cx) / fx, (i - cy) / fy, 1) in the camera frame (x right, y down, z
+    forward).  K: (3, 3) or (fx, fy, cx, cy); t_world_cam: (4, 4) rigid camera-to-world."""
+    K = np.asarray(K, np.float64)
+    fx, fy, cx, cy = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.reshape(4)
+    T = np.asarray(t_world_cam, np.float64).reshape(4, 4)
+    j, i = np.meshgrid(np.arange(int(width), dtype=np.float64), np.arange(int(height), dtype=np.float64))
+    d_cam = np.stack([(j - cx) / fx, (i - cy) / fy, np.ones_like(j)], -1).reshape(-1, 3)
+    dirs = (d_cam @ T[:3, :3].T).astype(np.float32)
+    origins = np.broadcast_to(T[:3, 3].astype(np.float32), dirs.shape).copy()
+    d64 = dirs.astype(np.float64)
+    u = d64 / np.sqrt((d64 * d64).sum(1))[:, None]
+    return origins, dirs, u @ T[:3, 2]                  # (R_cw u)_z = u . (third column of R_wc)
+
+
+def render(engine, objects, K, t_world_cam, width, height, normals=False, **params):
+    """What the map looks like from a pinhole camera: one ray per pixel centre (pixel_rays states the convention) through cast_rays.  A dict
+    of (height, width) images: `depth` (float32 z-depth t * (R_cw u)_z, +inf where nothing is hit), `id` (int64 map object id, -1 where
+    nothing is hit), `obj` (int32 index into `objects`), `status` (int32), `t`, `dist`, and with normals=True `normal` ((height, width, 3)
+    world unit normals, else None)."""
+    origins, dirs, cos = pixel_rays(K, t_world_cam, width, height)
+    res = cast_rays(engine, objects, origins, dirs, normals=normals, **params)
+    shape = (int(height), int(width))
+    with np.errstate(invalid="ignore"):
+        depth = np.where(res["obj"] >= 0, res["t"].astype(np.float64) * cos, np.inf).astype(np.float32)
+    out = {"depth": depth.reshape(shape), "id": res["id"].reshape(shape), "obj": res["obj"].reshape(shape), "status": res["status"].reshape(shape),
+           "t": res["t"].reshape(shape), "dist": res["dist"].reshape(shape), "normal": None}
+    if normals:
+        out["normal"] = res["normal"].reshape(shape + (3,))
+    return out
+
+
 def with_ids(result, ids):
     """result (an Engine.query_map dict) with `id` added: ids[obj] per point, -1 where obj is -1."""
     out = dict(result)

@@ -348,10 +348,59 @@ int dsp_debug_query_chunk_rows(dsp_handle* h, int64_t rows);
  * fewer from 8193 objects on.  DSP_E_ARG: a negative count, a budget or object count out of range. */
 int dsp_debug_query_plan(int64_t n_obj, const int32_t* cnt, int64_t budget, int64_t pass_n_obj, int64_t* sizes3, int32_t* chunks4, int32_t* base,
                          int32_t* tiles4, int64_t* pass_pts);
-/* Measurement: on != 0 brackets the following dsp_map_query calls on this handle, and every decoder launch inside them, with HIP events on
- * the handle's stream; ms2 (optional) receives {decoder launches, whole call} of the last such call in milliseconds (0, 0 before one).
- * The results of a call do not depend on it. */
+/* Measurement: on != 0 brackets the following dsp_map_query, dsp_map_align and dsp_map_raycast calls on this handle, and every decoder
+ * launch inside them, with HIP events on the handle's stream; ms2 (optional) receives {decoder launches, whole call} of the last such
+ * call in milliseconds (0, 0 before one).  The results of a call do not depend on it. */
 int dsp_debug_query_timing(dsp_handle* h, int on, double* ms2);
+
+/* ---- ray casting: what does the map look like from here?  First surface hit per world ray ----------------------------------------------
+ * For every ray (origin, direction; the direction need not be a unit vector, the parameter t is in world units along the unit direction)
+ * the call answers: the depth t of the first object surface, which object it belongs to, the signed distance dist (sdf * s) at the hit
+ * sample and -- with DSP_RAYCAST_NORMALS -- the surface's world-frame unit normal there.  Rays are marched by sphere tracing inside every
+ * object's unit sphere, with occlusion between objects: the smallest hit parameter wins, the lower object index among equal ones.
+ *   obj     the winning object, -1 for none        t     its hit parameter, +inf for none        dist   sdf * s at the hit, +inf for none
+ *   status  DSP_RAYCAST_HIT, DSP_RAYCAST_MISS, or DSP_RAYCAST_UNDECIDED: some (ray, object) pair took max_steps samples without ending,
+ *           at a parameter below the winner's t or with no winner at all; an UNDECIDED ray still reports the winner it has.
+ *   normal  zeros without a winner, and under the rule of dsp_map_query.
+ * A ray with a number that is not finite, or a zero direction, is void: -1, +inf, +inf, MISS; it disturbs no other ray.  An object whose
+ * code is not finite is never hit.  The arithmetic, the step rule and the occlusion retirement are written out in csrc/raycast_math.h, one
+ * correctly rounded fp32 operation at a time; the decoder rows are those of dsp_decode_sdf / dsp_sdf_jacobian at the object-frame
+ * samples, bit for bit, and the outputs do not depend on grid sizes, on the pass cut or on the order of reduction: two calls return the
+ * same bytes.  The march keeps its state, its compaction and its tile lists on the device; the host reads the pair counts once per call.
+ *
+ * params: t_min >= 0; t_max > t_min (+inf allowed); eps > 0, finite: a sample with dist <= eps is a hit; 0 < relax <= 1: the step is
+ * relax * dist; 1 <= max_steps <= 4096 samples per (ray, object) pair.  dsp_raycast_params_default: 0, +inf, 1e-3, 1, 64.
+ * The map is taken and checked as by dsp_map_query.  n_rays == 0 and n_obj == 0 are valid and touch no device.  DSP_E_ARG: a NULL
+ * argument (normal excepted), normal without the flag or the flag without normal, an unknown flag, params out of range, n_rays > 2^31 - 1,
+ * or a request too large for the fixed budgets -- 64 MiB of code biases (16 384 objects), 64 MiB of pair counts (objects x rays / 64):
+ * "split the request".  Pairs are marched in passes of at most the map query's chunk budget (dsp_debug_query_chunk_rows overrides it). */
+#define DSP_RAYCAST_NORMALS 1
+#define DSP_RAYCAST_MISS 0
+#define DSP_RAYCAST_HIT 1
+#define DSP_RAYCAST_UNDECIDED 2
+typedef struct dsp_raycast_params {
+    float t_min, t_max;     /* the parameter range of a hit */
+    float eps;              /* hit threshold on sdf * s, world units */
+    float relax;            /* step = relax * dist */
+    int32_t max_steps;      /* samples per (ray, object) pair */
+} dsp_raycast_params;
+void dsp_raycast_params_default(dsp_raycast_params* p);
+int dsp_map_raycast(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* origins, const float* dirs, int64_t n_rays,
+                    const dsp_raycast_params* params, int32_t flags, int32_t* obj, float* t, float* dist, int32_t* status, float* normal);
+/* Counts of the last dsp_map_raycast on this handle: counts6 = {(ray, object) pairs, decoder rows of the march, its tiles, rounds that
+ * decoded a row (summed over the passes), passes, exhausted pairs}.  The normals' rows are not counted.  Rows, tiles, rounds and exhausted
+ * pairs are a function of the inputs and of the pass cut (a pass retires pairs behind the hits of the passes before it); the outputs are not. */
+int dsp_map_raycast_last_stats(dsp_handle* h, int64_t* counts6);
+/* Host only, no handle: csrc/raycast_math.h on arrays.  dsp_debug_raycast_check: DSP_E_ARG for params dsp_map_raycast refuses.
+ * dsp_debug_raycast_segments: the map as dsp_debug_query_invert returns it (rt_ow, scale; a NaN scale stands for an object that is never
+ * hit) and n_rays rays -> is_void (n_rays bytes) and per pair, object major (n_obj x n_rays): exists (bytes), t0, t1, o_o and d_o (x 3);
+ * any output may be NULL; the pairs of a void ray read 0.  dsp_debug_raycast_step: n samples (t, t1, sdf, s) -> decision (0 hit, 1 miss
+ * on a NaN, 2 advance, 3 exit), dist and the next parameter (t itself for a hit or a NaN). */
+int dsp_debug_raycast_check(const dsp_raycast_params* params);
+int dsp_debug_raycast_segments(int64_t n_obj, const float* rt_ow, const float* scale, int64_t n_rays, const float* origins, const float* dirs, float t_min,
+                               float t_max, unsigned char* is_void, unsigned char* exists, float* t0, float* t1, float* o_o, float* d_o);
+int dsp_debug_raycast_step(int64_t n, const float* t, const float* t1, const float* sdf, const float* s, const dsp_raycast_params* params,
+                           int32_t* decision, float* dist, float* t_next);
 
 /* ---- map alignment: where is the sensor, given points in its frame and the map?  Batched SE(3) Gauss-Newton ---------------------------
  * n_hyp initial sensor-to-world poses (hypotheses: a relocaliser's seeds, the yaw alternatives of the mono path) are refined against the

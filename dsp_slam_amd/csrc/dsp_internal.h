@@ -618,10 +618,24 @@ hipError_t launch_align_winner(const float* rows, const int2* row_meta, int n_ro
 hipError_t launch_align_gram(const float* pts_w, const int* obj, const float* dist, const float* grad_w, const float* weights, int64_t n_pts, int n_hyp,
                              const float* hyp, double huber, double max_dist, double* slab, double* sums, hipStream_t s);
 int64_t align_gram_blocks(int64_t n_pts);
+// Ray alignment (the arithmetic: align_rays_math.h).  build: rows [0, n) of pts_w / org_w / dir_w <- the world end point, origin and
+// direction of observation i under hypothesis h (org_s null: the sensor origin), NaN for an ended hypothesis.  gradient: behind a chunk of
+// the winners' jacobian rows (row_meta = {row of the cast, object}), the world gradient of d.  residual: the cast's answers -> obj_row, d_row,
+// which launch_align_gram reads as obj and dist.
+hipError_t launch_align_rays_build(const float* pts_s, const float* org_s, int64_t n_rays, const float* hyp, int64_t n, float* pts_w, float* org_w,
+                                   float* dir_w, hipStream_t s);
+hipError_t launch_align_rays_gradient(const float* rows, const int2* row_meta, int n_rows, const float* tab, int n_obj, int64_t n_rays, float* grad_w,
+                                      hipStream_t s);
+hipError_t launch_align_rays_residual(const float* org_w, const float* dir_w, const int* obj, const float* t_hit, const float* dist_hit, const int* status,
+                                      const float* grad_w, int64_t n, double max_gap, int* obj_row, float* d_row, hipStream_t s);
 // align_math.h compiled for the host in the translation unit that has contraction off (dsp_map_align's step, dsp_debug_align_*)
 bool align_check_pose_host(const double* t16, float* rt12);
 void align_rows_host(int64_t n, const float* pts_w, const int32_t* obj, const float* dist, const float* grad_w, const float* weights, double huber,
                      double max_dist, double* sums);
+void align_ray_rows_host(int64_t n, const float* org_w, const float* pts_w, const int32_t* obj, const float* t_hit, const float* dist_hit,
+                         const int32_t* status, const float* grad_w, const float* weights, double huber, double max_dist, double max_gap,
+                         int32_t* obj_row, float* d_row, double* sums);
+const char* align_rays_check_gap_host(double max_gap, double max_dist);
 double align_cost_host(const double* sums, double huber, double max_dist);
 bool align_solve_host(const double* H36, const double* b6, double damp, double lambda, double* xi6);
 void align_apply_step_host(const double* xi6, const double* t_in, double* t_out);

@@ -1,9 +1,10 @@
 // The object map on the host: signed distance and normal of world points (dsp_map_query) and the alignment of a point cloud to the map
-// (dsp_map_align), which runs the query's core; with their C ABI.
+// (dsp_map_align), which runs the query's core; ray casting (dsp_map_raycast) and the alignment of depth rays to the map
+// (dsp_map_align_rays), which runs the cast's core inside the alignment's hypothesis loop; with their C ABI.
 #include "decoder_calls.h"
 #include "decoder_pack.h"
 #include "query_math.h"     // constants only: the arithmetic is compiled in query_kernels.hip (contraction off)
-#include "align_math.h"     // constants only, likewise (align_kernels.hip)
+#include "align_math.h"     // constants only, likewise (align_kernels.hip; the ray alignment's arithmetic, align_rays_math.h, is compiled there too)
 
 #include <algorithm>
 #include <cmath>
@@ -304,6 +305,161 @@ std::vector<RaycastPassHost> raycast_passes(const int* cnt, int64_t n_obj, int64
     return passes;
 }
 
+// nullptr, or why a cast of n_rays rays against n_obj objects is refused: its tables would exceed the fixed budgets above
+const char* raycast_check_size(int64_t n_obj, int64_t n_rays) {
+    const int64_t n_waves = (n_rays + 63) / 64;
+    if (n_obj > 0 && n_rays > 0 &&
+        ((size_t)n_obj * 2 * WIDTH * sizeof(float) > RAYCAST_CBIAS_BYTES || (size_t)n_obj * (size_t)n_waves * sizeof(int) > QUERY_WAVECNT_BYTES))
+        return "raycast: objects x rays too large (split the request)";
+    return nullptr;
+}
+
+// The device blocks and the host uploads of a cast.  They belong to the caller and live until the stream has been synchronised behind the
+// cast; a caller that casts again (dsp_map_align_rays, once per evaluation) reuses them.  The answers stay on the device: r_obj, r_t,
+// r_dist, r_status per ray.
+struct RaycastWork {
+    DevBuf<float> r_t, r_dist, p_t, p_t1, p_dist, p_out, n_out;
+    DevBuf<unsigned long long> r_best, r_dstats;
+    DevBuf<unsigned> r_exh;
+    DevBuf<int> r_obj, r_status, r_wave_cnt, r_cnt, p_state, p_live, p_wrow, p_ctrl, p_rslot, n_base, n_ntiles;
+    DevBuf<int2> p_wtab, p_meta, n_meta;
+    DevBuf<int4> p_pobj, p_ob, p_oinfo, p_tiles, n_tiles;
+    DevBuf<float4> p_oo, p_do, p_pts, n_pts;
+    std::vector<int> cnt;
+    std::vector<RaycastPassHost> passes;        // the uploads of the passes in flight are copied from here ...
+    std::vector<QueryChunk> plan;               // ... and those of the winners' chunks from here
+    unsigned long long dstats[4] = {0, 0, 0, 0};
+};
+
+using RaycastRows = std::function<void(const RaycastDev&, const float* rows, const int2* row_meta, int n_rows)>;
+
+// The device-resident cast: n_rays world rays (org, dir: packed float3), the object table and the code biases of all objects (2 * WIDTH floats
+// each) on the device in; the answers in w.r_* on the device.  behind_rows (may be empty: no winner rows are decoded) is called behind every
+// chunk of the winners' jacobian rows -- the hit samples grouped by object in ascending ray order -- with row_meta = {ray, object}.  normal
+// (may be null) is only zeroed here where a ray has no winner.  Synchronises for the pair counts, the live polls and the winners' counts; the
+// caller synchronises behind it before w's uploads die, then calls raycast_core_stats.  stats6[0], [4] += pairs, passes.  n_rays, n_obj > 0.
+void raycast_core(dsp_handle* h, RaycastWork& w, const float* org, const float* dir, const float* tab, const float* cbias, int64_t n_obj, int64_t n_rays,
+                  const raycast_math::Params& prm, float* normal, QueryTimer& timer, int64_t* stats6, const RaycastRows& behind_rows) {
+    const int64_t n_waves = (n_rays + 63) / 64;
+    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : query_default_budget();
+    w.cnt.resize((size_t)n_obj);
+    w.r_best.ensure((size_t)n_rays);
+    w.r_exh.ensure((size_t)n_rays);
+    w.r_obj.ensure((size_t)n_rays);
+    w.r_t.ensure((size_t)n_rays);
+    w.r_dist.ensure((size_t)n_rays);
+    w.r_status.ensure((size_t)n_rays);
+    w.r_dstats.ensure(4);
+    w.r_wave_cnt.ensure((size_t)n_obj * n_waves);
+    w.r_cnt.ensure((size_t)n_obj);
+    h->s_clk.ensure(4);
+    HIP_TRY(hipMemsetAsync(w.r_dstats.p, 0, sizeof w.dstats, h->stream));
+    const RaycastDev d{org, dir, tab, (int)n_rays, (int)n_obj, (int)n_waves, prm, w.r_best.p, w.r_exh.p, w.r_obj.p, w.r_t.p, w.r_dist.p, w.r_status.p,
+                       normal, w.r_dstats.p};
+    HIP_TRY(launch_raycast_count(d, w.r_wave_cnt.p, w.r_cnt.p, h->stream));
+    HIP_TRY(hipMemcpyAsync(w.cnt.data(), w.r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));           // the pair counts, once per cast
+    w.passes = raycast_passes(w.cnt.data(), n_obj, budget);
+    for (int c : w.cnt) stats6[0] += c;
+    stats6[4] += (int64_t)w.passes.size();
+    size_t max_slots = 0, max_nc = 0;
+    for (const RaycastPassHost& p : w.passes) { max_slots = std::max<size_t>(max_slots, p.n_slots); max_nc = std::max<size_t>(max_nc, p.nc); }
+    if (!w.passes.empty()) {
+        w.p_pobj.ensure(max_nc); w.p_ob.ensure(max_nc); w.p_oinfo.ensure(max_nc);
+        w.p_wtab.ensure(max_slots / 64); w.p_live.ensure(max_slots / 64); w.p_wrow.ensure(max_slots / 64); w.p_tiles.ensure(max_slots / 64);
+        w.p_meta.ensure(max_slots); w.p_state.ensure(max_slots); w.p_t.ensure(max_slots); w.p_t1.ensure(max_slots); w.p_dist.ensure(max_slots);
+        w.p_oo.ensure(max_slots); w.p_do.ensure(max_slots); w.p_pts.ensure(max_slots); w.p_rslot.ensure(max_slots); w.p_out.ensure(max_slots);
+        w.p_ctrl.ensure(2);
+    }
+    for (const RaycastPassHost& ph : w.passes) {
+        if (ph.n_slots <= 0) continue;
+        const RaycastPass p{ph.o0, ph.nc, ph.n_slots, w.p_pobj.p, w.p_ob.p, w.p_wtab.p, w.p_meta.p, w.p_state.p, w.p_t.p, w.p_t1.p, w.p_dist.p, w.p_oo.p,
+                            w.p_do.p, w.p_live.p, w.p_wrow.p, w.p_oinfo.p, w.p_ctrl.p, w.p_pts.p, w.p_rslot.p, w.p_tiles.p};
+        HIP_TRY(hipMemcpyAsync(w.p_pobj.p, ph.pobj.data(), ph.pobj.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(w.p_ob.p, ph.ob.data(), ph.ob.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(w.p_wtab.p, ph.wtab.data(), ph.wtab.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemsetAsync(w.p_state.p, 0xff, (size_t)ph.n_slots * sizeof(int), h->stream));       // padding: neither live nor hit
+        HIP_TRY(hipMemsetAsync(w.p_meta.p, 0xff, (size_t)ph.n_slots * sizeof(int2), h->stream));
+        HIP_TRY(launch_raycast_fill(d, p, w.r_wave_cnt.p, h->stream));
+        MlpArgs a = make_mlp_args(h, 0);
+        a.n_tiles = w.p_ctrl.p;
+        a.tiles = w.p_tiles.p;
+        a.pts = w.p_pts.p;
+        a.code_bias = cbias;
+        a.code_bias_stride = 2 * WIDTH;
+        a.out_sdf = w.p_out.p;
+        a.out_grad = w.p_out.p;
+        a.clk = h->s_clk.p;
+        const int grid = std::min(ph.n_slots / 64, h->n_cu);
+        for (int round = 0; round < prm.max_steps; ++round) {
+            HIP_TRY(launch_raycast_round_front(d, p, h->stream));
+            timer.mark();
+            HIP_TRY(launch_mlp(0, a, grid, h->stream));
+            timer.mark();
+            HIP_TRY(launch_raycast_step(d, p, w.p_out.p, h->stream));
+            if ((round + 1) % RAYCAST_POLL_ROUNDS == 0 && round + 1 < prm.max_steps) {
+                int live = 0;
+                HIP_TRY(hipMemcpyAsync(&live, w.p_ctrl.p + 1, sizeof live, hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                if (live == 0) break;           // the round just run decoded nothing: no later one would
+            }
+        }
+        HIP_TRY(launch_raycast_end(d, p, h->stream));
+    }
+    HIP_TRY(launch_raycast_finish(d, h->stream));
+    if (behind_rows) {  // the winners' hit samples through the jacobian form, grouped by object in ascending ray order
+        HIP_TRY(launch_raycast_wincount(d, w.r_wave_cnt.p, w.r_cnt.p, h->stream));
+        HIP_TRY(hipMemcpyAsync(w.cnt.data(), w.r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        w.plan = query_plan_geometry(w.cnt.data(), n_obj, budget);
+        size_t max_rows = 0, max_nt = 0, max_base = 0;
+        for (QueryChunk& c : w.plan) {
+            for (int4& tile : c.tiles) tile.z = c.slot_obj[tile.z];        // the slot of the call's code-bias table: the object itself
+            max_rows = std::max<size_t>(max_rows, c.n_rows); max_nt = std::max<size_t>(max_nt, c.nt); max_base = std::max<size_t>(max_base, c.nc);
+        }
+        if (!w.plan.empty()) {
+            w.n_pts.ensure(max_rows); w.n_out.ensure(max_rows * GRAD_STRIDE); w.n_meta.ensure(max_rows); w.n_tiles.ensure(max_nt); w.n_base.ensure(max_base);
+            w.n_ntiles.ensure(1);
+        }
+        for (const QueryChunk& c : w.plan) {
+            HIP_TRY(hipMemcpyAsync(w.n_tiles.p, c.tiles.data(), c.nt * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(w.n_ntiles.p, &c.nt, 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(w.n_base.p, c.base.data(), c.nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(launch_raycast_winfill(d, c.o0, c.nc, w.n_base.p, w.r_wave_cnt.p, c.n_rows, w.n_pts.p, w.n_meta.p, h->stream));
+            MlpArgs a = make_mlp_args(h, 2);
+            a.n_tiles = w.n_ntiles.p;
+            a.tiles = w.n_tiles.p;
+            a.pts = w.n_pts.p;
+            a.code_bias = cbias;
+            a.code_bias_stride = 2 * WIDTH;
+            a.out_sdf = w.n_out.p;
+            a.out_grad = w.n_out.p;
+            a.clk = h->s_clk.p;
+            timer.mark();
+            HIP_TRY(launch_mlp(2, a, std::min(c.nt, h->n_cu), h->stream));
+            timer.mark();
+            behind_rows(d, w.n_out.p, w.n_meta.p, c.n_rows);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(w.dstats, w.r_dstats.p, sizeof w.dstats, hipMemcpyDeviceToHost, h->stream));
+}
+
+// behind the synchronisation that follows raycast_core: stats6[1], [2], [3], [5] += decoder rows, tiles, rounds, exhausted pairs
+void raycast_core_stats(const RaycastWork& w, int64_t* stats6) {
+    stats6[1] += (int64_t)w.dstats[0];
+    stats6[2] += (int64_t)w.dstats[1];
+    stats6[3] += (int64_t)w.dstats[2];
+    stats6[5] += (int64_t)w.dstats[3];
+}
+
+// the code biases of all objects of a call: 2 * WIDTH floats each
+std::vector<float> raycast_code_biases(const dsp_handle* h, const float* codes, int64_t n_obj) {
+    std::vector<float> cb((size_t)n_obj * 2 * WIDTH);
+    for (int64_t o = 0; o < n_obj; ++o) code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + (size_t)o * CODE_LEN, cb.data() + (size_t)o * 2 * WIDTH);
+    return cb;
+}
+
+// dsp_map_raycast: host rays up, raycast_core, host answers down
 void raycast_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* org, const float* dir, int64_t n_rays,
                  const raycast_math::Params& prm, int32_t* obj, float* t, float* dist, int32_t* status, float* normal) {
     for (auto& c : h->r_stats) c = 0;
@@ -317,149 +473,41 @@ void raycast_run(dsp_handle* h, const std::vector<float>& tab, const float* code
         }
         return;
     }
-    const int64_t n_waves = (n_rays + 63) / 64;
-    if ((size_t)n_obj * 2 * WIDTH * sizeof(float) > RAYCAST_CBIAS_BYTES || (size_t)n_obj * (size_t)n_waves * sizeof(int) > QUERY_WAVECNT_BYTES)
-        throw std::invalid_argument("raycast: objects x rays too large (split the request)");
-    const int64_t budget = h->q_chunk_rows > 0 ? h->q_chunk_rows : query_default_budget();
+    if (const char* why = raycast_check_size(n_obj, n_rays)) throw std::invalid_argument(why);
     HIP_TRY(hipSetDevice(h->device));
-    DevBuf<float> r_org, r_dir, r_tab, r_t, r_dist, r_normal, r_cb, p_t, p_t1, p_dist, p_out, n_out;
-    DevBuf<unsigned long long> r_best, r_dstats;
-    DevBuf<unsigned> r_exh;
-    DevBuf<int> r_obj, r_status, r_wave_cnt, r_cnt, p_state, p_live, p_wrow, p_ctrl, p_rslot, n_base, n_ntiles;
-    DevBuf<int2> p_wtab, p_meta, n_meta;
-    DevBuf<int4> p_pobj, p_ob, p_oinfo, p_tiles, n_tiles;
-    DevBuf<float4> p_oo, p_do, p_pts, n_pts;
-    std::vector<int> cnt((size_t)n_obj);
-    std::vector<float> cb((size_t)n_obj * 2 * WIDTH);
-    std::vector<RaycastPassHost> passes;        // the uploads of the passes in flight are copied from here ...
-    std::vector<QueryChunk> plan;               // ... and those of the normals' chunks from here
-    unsigned long long dstats[4] = {0, 0, 0, 0};
+    DevBuf<float> r_org, r_dir, r_tab, r_normal, r_cb;
+    RaycastWork w;
+    std::vector<float> cb;
     SyncOnExit sync_on_exit{h->stream};
     QueryTimer timer{h->q_timing, h->stream, {}};
     h->q_ms[0] = h->q_ms[1] = 0.0;
     timer.mark();
-    for (int64_t o = 0; o < n_obj; ++o) code_bias_host(h->h_codew, h->h_b0, h->h_blat, codes + (size_t)o * CODE_LEN, cb.data() + (size_t)o * 2 * WIDTH);
+    cb = raycast_code_biases(h, codes, n_obj);
     r_org.alloc((size_t)n_rays * 3);
     r_dir.alloc((size_t)n_rays * 3);
     r_tab.alloc(tab.size());
     r_cb.alloc(cb.size());
-    r_best.alloc((size_t)n_rays);
-    r_exh.alloc((size_t)n_rays);
-    r_obj.alloc((size_t)n_rays);
-    r_t.alloc((size_t)n_rays);
-    r_dist.alloc((size_t)n_rays);
-    r_status.alloc((size_t)n_rays);
     if (normal) r_normal.alloc((size_t)n_rays * 3);
-    r_dstats.alloc(4);
-    r_wave_cnt.alloc((size_t)n_obj * n_waves);
-    r_cnt.alloc((size_t)n_obj);
-    h->s_clk.ensure(4);
     HIP_TRY(hipMemcpyAsync(r_org.p, org, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(r_dir.p, dir, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(r_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(r_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(r_dstats.p, 0, sizeof dstats, h->stream));
-    const RaycastDev d{r_org.p, r_dir.p, r_tab.p, (int)n_rays, (int)n_obj, (int)n_waves, prm, r_best.p, r_exh.p, r_obj.p, r_t.p, r_dist.p, r_status.p,
-                       normal ? r_normal.p : nullptr, r_dstats.p};
-    HIP_TRY(launch_raycast_count(d, r_wave_cnt.p, r_cnt.p, h->stream));
-    HIP_TRY(hipMemcpyAsync(cnt.data(), r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));           // the pair counts, once per call
-    passes = raycast_passes(cnt.data(), n_obj, budget);
-    for (int c : cnt) h->r_stats[0] += c;
-    h->r_stats[4] = (int64_t)passes.size();
-    size_t max_slots = 0, max_nc = 0;
-    for (const RaycastPassHost& p : passes) { max_slots = std::max<size_t>(max_slots, p.n_slots); max_nc = std::max<size_t>(max_nc, p.nc); }
-    if (!passes.empty()) {
-        p_pobj.alloc(max_nc); p_ob.alloc(max_nc); p_oinfo.alloc(max_nc);
-        p_wtab.alloc(max_slots / 64); p_live.alloc(max_slots / 64); p_wrow.alloc(max_slots / 64); p_tiles.alloc(max_slots / 64);
-        p_meta.alloc(max_slots); p_state.alloc(max_slots); p_t.alloc(max_slots); p_t1.alloc(max_slots); p_dist.alloc(max_slots);
-        p_oo.alloc(max_slots); p_do.alloc(max_slots); p_pts.alloc(max_slots); p_rslot.alloc(max_slots); p_out.alloc(max_slots);
-        p_ctrl.alloc(2);
-    }
-    for (const RaycastPassHost& ph : passes) {
-        if (ph.n_slots <= 0) continue;
-        const RaycastPass p{ph.o0, ph.nc, ph.n_slots, p_pobj.p, p_ob.p, p_wtab.p, p_meta.p, p_state.p, p_t.p, p_t1.p, p_dist.p, p_oo.p, p_do.p,
-                            p_live.p, p_wrow.p, p_oinfo.p, p_ctrl.p, p_pts.p, p_rslot.p, p_tiles.p};
-        HIP_TRY(hipMemcpyAsync(p_pobj.p, ph.pobj.data(), ph.pobj.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(p_ob.p, ph.ob.data(), ph.ob.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(p_wtab.p, ph.wtab.data(), ph.wtab.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemsetAsync(p_state.p, 0xff, (size_t)ph.n_slots * sizeof(int), h->stream));         // padding: neither live nor hit
-        HIP_TRY(hipMemsetAsync(p_meta.p, 0xff, (size_t)ph.n_slots * sizeof(int2), h->stream));
-        HIP_TRY(launch_raycast_fill(d, p, r_wave_cnt.p, h->stream));
-        MlpArgs a = make_mlp_args(h, 0);
-        a.n_tiles = p_ctrl.p;
-        a.tiles = p_tiles.p;
-        a.pts = p_pts.p;
-        a.code_bias = r_cb.p;
-        a.code_bias_stride = 2 * WIDTH;
-        a.out_sdf = p_out.p;
-        a.out_grad = p_out.p;
-        a.clk = h->s_clk.p;
-        const int grid = std::min(ph.n_slots / 64, h->n_cu);
-        for (int round = 0; round < prm.max_steps; ++round) {
-            HIP_TRY(launch_raycast_round_front(d, p, h->stream));
-            timer.mark();
-            HIP_TRY(launch_mlp(0, a, grid, h->stream));
-            timer.mark();
-            HIP_TRY(launch_raycast_step(d, p, p_out.p, h->stream));
-            if ((round + 1) % RAYCAST_POLL_ROUNDS == 0 && round + 1 < prm.max_steps) {
-                int live = 0;
-                HIP_TRY(hipMemcpyAsync(&live, p_ctrl.p + 1, sizeof live, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                if (live == 0) break;           // the round just run decoded nothing: no later one would
-            }
-        }
-        HIP_TRY(launch_raycast_end(d, p, h->stream));
-    }
-    HIP_TRY(launch_raycast_finish(d, h->stream));
-    if (normal) {       // the winners' hit samples through the jacobian form, grouped by object in ascending ray order
-        HIP_TRY(launch_raycast_wincount(d, r_wave_cnt.p, r_cnt.p, h->stream));
-        HIP_TRY(hipMemcpyAsync(cnt.data(), r_cnt.p, (size_t)n_obj * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        plan = query_plan_geometry(cnt.data(), n_obj, budget);
-        size_t max_rows = 0, max_nt = 0, max_base = 0;
-        for (QueryChunk& c : plan) {
-            for (int4& tile : c.tiles) tile.z = c.slot_obj[tile.z];        // the slot of the call's code-bias table: the object itself
-            max_rows = std::max<size_t>(max_rows, c.n_rows); max_nt = std::max<size_t>(max_nt, c.nt); max_base = std::max<size_t>(max_base, c.nc);
-        }
-        if (!plan.empty()) {
-            n_pts.alloc(max_rows); n_out.alloc(max_rows * GRAD_STRIDE); n_meta.alloc(max_rows); n_tiles.alloc(max_nt); n_base.alloc(max_base);
-            n_ntiles.alloc(1);
-        }
-        for (const QueryChunk& c : plan) {
-            HIP_TRY(hipMemcpyAsync(n_tiles.p, c.tiles.data(), c.nt * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(n_ntiles.p, &c.nt, 4, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(n_base.p, c.base.data(), c.nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(launch_raycast_winfill(d, c.o0, c.nc, n_base.p, r_wave_cnt.p, c.n_rows, n_pts.p, n_meta.p, h->stream));
-            MlpArgs a = make_mlp_args(h, 2);
-            a.n_tiles = n_ntiles.p;
-            a.tiles = n_tiles.p;
-            a.pts = n_pts.p;
-            a.code_bias = r_cb.p;
-            a.code_bias_stride = 2 * WIDTH;
-            a.out_sdf = n_out.p;
-            a.out_grad = n_out.p;
-            a.clk = h->s_clk.p;
-            timer.mark();
-            HIP_TRY(launch_mlp(2, a, std::min(c.nt, h->n_cu), h->stream));
-            timer.mark();
-            HIP_TRY(launch_raycast_normal(d, n_out.p, n_meta.p, c.n_rows, h->stream));
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(obj, r_obj.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(t, r_t.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(dist, r_dist.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(status, r_status.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    RaycastRows normals;
+    if (normal)
+        normals = [&](const RaycastDev& d, const float* rows, const int2* row_meta, int n_rows) {
+            HIP_TRY(launch_raycast_normal(d, rows, row_meta, n_rows, h->stream));
+        };
+    raycast_core(h, w, r_org.p, r_dir.p, r_tab.p, r_cb.p, n_obj, n_rays, prm, normal ? r_normal.p : nullptr, timer, h->r_stats, normals);
+    HIP_TRY(hipMemcpyAsync(obj, w.r_obj.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(t, w.r_t.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dist, w.r_dist.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(status, w.r_status.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
     if (normal) HIP_TRY(hipMemcpyAsync(normal, r_normal.p, (size_t)n_rays * 12, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(dstats, r_dstats.p, sizeof dstats, hipMemcpyDeviceToHost, h->stream));
     timer.mark();
-    HIP_TRY(hipStreamSynchronize(h->stream));           // `passes` and `plan` (the uploads) live until here
+    HIP_TRY(hipStreamSynchronize(h->stream));           // w's uploads live until here
     HIP_TRY(hipGetLastError());
     timer.read(h->q_ms);
-    h->r_stats[1] = (int64_t)dstats[0];
-    h->r_stats[2] = (int64_t)dstats[1];
-    h->r_stats[3] = (int64_t)dstats[2];
-    h->r_stats[5] = (int64_t)dstats[3];
+    raycast_core_stats(w, h->r_stats);
 }
 
 raycast_math::Params raycast_params(const dsp_raycast_params& p) { return raycast_math::Params{p.t_min, p.t_max, p.eps, p.relax, p.max_steps}; }
@@ -510,67 +558,39 @@ void align_write(const AlignHyp& a, double* T_out, double* rec) {
     for (int i = 0; i < 6; ++i) rec[44 + i] = a.S[align_math::IDX_B + i];
 }
 
-// Points and weights are uploaded once; per evaluation the host sends the hypotheses' fp32 poses and reads the query's candidate counts
-// (once per pass) and align_math::NSUM doubles per hypothesis.  The step lives on the host.
-void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* pts, const float* weights, int64_t n_pts,
-               const double* T0, int64_t n_hyp, const dsp_align_params& prm, double* T_out, double* record, int32_t* obj, float* dist, double* trace) {
-    constexpr int NS = align_math::NSUM;
-    for (auto& c : h->a_stats) c = 0;
-    const step_rule::Params sp{prm.lambda0, prm.up, prm.down, prm.lambda_min, prm.lambda_max};
-    const bool step_on = !step_rule::is_off(sp);
-    const int iters = prm.iterations;
+std::vector<AlignHyp> align_start(const double* T0, int64_t n_hyp) {
     std::vector<AlignHyp> hyp((size_t)n_hyp);
     for (int64_t k = 0; k < n_hyp; ++k) {
         memcpy(hyp[k].T_acc, T0 + 16 * k, sizeof hyp[k].T_acc);
         memcpy(hyp[k].T_eval, T0 + 16 * k, sizeof hyp[k].T_eval);
         for (double& s : hyp[k].S) s = 0.0;
     }
-    if (trace) std::fill(trace, trace + (size_t)n_hyp * iters * DSP_ALIGN_TRACE, 0.0);
-    if (n_hyp == 0) return;
-    if (n_pts == 0 || n_obj == 0) {             // nothing to evaluate: no support at the input pose
-        double zero[NS] = {};
-        for (int64_t k = 0; k < n_hyp; ++k) {
-            hyp[k].status = DSP_ALIGN_NO_SUPPORT;
-            hyp[k].F0 = hyp[k].F_acc = align_cost_host(zero, prm.huber, prm.max_dist);
-            align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
-        }
-        if (obj)
-            for (int64_t r = 0; r < n_hyp * n_pts; ++r) { obj[r] = -1; dist[r] = INFINITY; }
-        return;
+    return hyp;
+}
+
+// nothing to evaluate: no support at the input pose
+void align_write_no_support(std::vector<AlignHyp>& hyp, const dsp_align_params& prm, double* T_out, double* record) {
+    double zero[align_math::NSUM] = {};
+    for (size_t k = 0; k < hyp.size(); ++k) {
+        hyp[k].status = DSP_ALIGN_NO_SUPPORT;
+        hyp[k].F0 = hyp[k].F_acc = align_cost_host(zero, prm.huber, prm.max_dist);
+        align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t n_rows = n_hyp * n_pts, nb = align_gram_blocks(n_pts);
-    DevBuf<float> a_pts, a_w, a_hyp, a_grad, q_tab, q_pw, q_bound, q_dist, r_dist;
-    DevBuf<unsigned long long> q_best;
-    DevBuf<int> q_obj, r_obj;
-    DevBuf<double> a_slab, a_sums;
-    std::vector<QueryChunk> plan;               // the uploads of the pass in flight are copied from here ...
-    std::vector<float> hyp_tab((size_t)n_hyp * ALIGN_HYP_STRIDE, 0.f);      // ... and the evaluation's poses from here
+}
+
+// The hypothesis loop of dsp_map_align and dsp_map_align_rays: statuses, step control, convergence rule, Cholesky and exp_se3; the step lives
+// on the host.  evaluate(hyp_tab, sums) runs one evaluation of every live hypothesis at the fp32 poses of hyp_tab (ALIGN_HYP_STRIDE floats
+// per hypothesis; it uploads them) and returns with align_math::NSUM sums per hypothesis on the host and the stream idle.  accepted(k) is
+// called when hypothesis k's evaluation becomes its returned state.  *n_evals += 1 per evaluation.
+void align_loop(std::vector<AlignHyp>& hyp, const dsp_align_params& prm, double* trace, int64_t* n_evals,
+                const std::function<void(const std::vector<float>&, std::vector<double>&)>& evaluate, const std::function<void(int64_t)>& accepted) {
+    constexpr int NS = align_math::NSUM;
+    const int64_t n_hyp = (int64_t)hyp.size();
+    const step_rule::Params sp{prm.lambda0, prm.up, prm.down, prm.lambda_min, prm.lambda_max};
+    const bool step_on = !step_rule::is_off(sp);
+    const int iters = prm.iterations;
+    std::vector<float> hyp_tab((size_t)n_hyp * ALIGN_HYP_STRIDE, 0.f);
     std::vector<double> sums((size_t)n_hyp * NS, 0.0);
-    SyncOnExit sync_on_exit{h->stream};
-    QueryTimer timer{h->q_timing, h->stream, {}};
-    h->q_ms[0] = h->q_ms[1] = 0.0;
-    timer.mark();
-    a_pts.alloc((size_t)n_pts * 3);
-    if (weights) a_w.alloc((size_t)n_pts);
-    a_hyp.alloc(hyp_tab.size());
-    a_grad.alloc((size_t)n_rows * 3);
-    q_tab.alloc(tab.size());
-    q_pw.alloc((size_t)n_rows * 3);
-    q_bound.alloc((size_t)n_rows);
-    q_dist.alloc((size_t)n_rows);
-    q_obj.alloc((size_t)n_rows);
-    q_best.alloc((size_t)n_rows);
-    if (obj) { r_obj.alloc((size_t)n_rows); r_dist.alloc((size_t)n_rows); }
-    a_slab.alloc((size_t)n_hyp * nb * NS);
-    a_sums.alloc(sums.size());
-    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_pts * 12, hipMemcpyHostToDevice, h->stream));
-    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_pts * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
-    const QueryDev d{q_pw.p, q_tab.p, q_bound.p, q_best.p, q_obj.p, q_dist.p, nullptr};
-    const std::function<void(const QueryChunk&)> winner = [&](const QueryChunk& c) {
-        HIP_TRY(launch_align_winner(h->s_out.p, h->q_row_meta.p, c.n_rows, q_tab.p, (int)n_obj, n_rows, q_best.p, a_grad.p, h->stream));
-    };
     auto end = [](AlignHyp& a, int status) { a.live = false; a.status = status; };
     for (int e = 0; e < iters; ++e) {
         bool any = false;
@@ -581,14 +601,8 @@ void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes,
             any = any || hyp[k].live;
         }
         if (!any) break;
-        HIP_TRY(hipMemcpyAsync(a_hyp.p, hyp_tab.data(), hyp_tab.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(launch_align_transform(a_pts.p, n_pts, a_hyp.p, 0, n_rows, q_pw.p, h->stream));
-        query_core(h, codes, n_obj, n_rows, d, true, plan, timer, h->a_stats, winner);
-        HIP_TRY(launch_align_gram(q_pw.p, q_obj.p, q_dist.p, a_grad.p, weights ? a_w.p : nullptr, n_pts, (int)n_hyp, a_hyp.p, prm.huber, prm.max_dist,
-                                  a_slab.p, a_sums.p, h->stream));
-        HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));       // the sums; `plan` and hyp_tab have been consumed
-        h->a_stats[4] += 1;
+        evaluate(hyp_tab, sums);
+        *n_evals += 1;
         for (int64_t k = 0; k < n_hyp; ++k) {
             AlignHyp& a = hyp[k];
             if (!a.live) continue;
@@ -608,10 +622,7 @@ void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes,
                 memcpy(a.S, S, sizeof a.S);
                 a.F_acc = F;
                 a.has_acc = true;
-                if (obj) {      // the per-point outputs belong to the returned state
-                    HIP_TRY(hipMemcpyAsync(r_obj.p + k * n_pts, q_obj.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
-                    HIP_TRY(hipMemcpyAsync(r_dist.p + k * n_pts, q_dist.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
-                }
+                if (accepted) accepted(k);      // the per-observation outputs belong to the returned state
             }
             if (tr) {
                 memcpy(tr, a.T_eval, sizeof a.T_eval);
@@ -639,9 +650,173 @@ void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes,
             align_apply_step_host(xi, a.T_acc, a.T_eval);
         }
     }
+}
+
+// Points and weights are uploaded once; per evaluation the host sends the hypotheses' fp32 poses and reads the query's candidate counts
+// (once per pass) and align_math::NSUM doubles per hypothesis.
+void align_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* pts, const float* weights, int64_t n_pts,
+               const double* T0, int64_t n_hyp, const dsp_align_params& prm, double* T_out, double* record, int32_t* obj, float* dist, double* trace) {
+    constexpr int NS = align_math::NSUM;
+    for (auto& c : h->a_stats) c = 0;
+    std::vector<AlignHyp> hyp = align_start(T0, n_hyp);
+    if (trace) std::fill(trace, trace + (size_t)n_hyp * prm.iterations * DSP_ALIGN_TRACE, 0.0);
+    if (n_hyp == 0) return;
+    if (n_pts == 0 || n_obj == 0) {
+        align_write_no_support(hyp, prm, T_out, record);
+        if (obj)
+            for (int64_t r = 0; r < n_hyp * n_pts; ++r) { obj[r] = -1; dist[r] = INFINITY; }
+        return;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_rows = n_hyp * n_pts, nb = align_gram_blocks(n_pts);
+    DevBuf<float> a_pts, a_w, a_hyp, a_grad, q_tab, q_pw, q_bound, q_dist, r_dist;
+    DevBuf<unsigned long long> q_best;
+    DevBuf<int> q_obj, r_obj;
+    DevBuf<double> a_slab, a_sums;
+    std::vector<QueryChunk> plan;               // the uploads of the pass in flight are copied from here
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    a_pts.alloc((size_t)n_pts * 3);
+    if (weights) a_w.alloc((size_t)n_pts);
+    a_hyp.alloc((size_t)n_hyp * ALIGN_HYP_STRIDE);
+    a_grad.alloc((size_t)n_rows * 3);
+    q_tab.alloc(tab.size());
+    q_pw.alloc((size_t)n_rows * 3);
+    q_bound.alloc((size_t)n_rows);
+    q_dist.alloc((size_t)n_rows);
+    q_obj.alloc((size_t)n_rows);
+    q_best.alloc((size_t)n_rows);
+    if (obj) { r_obj.alloc((size_t)n_rows); r_dist.alloc((size_t)n_rows); }
+    a_slab.alloc((size_t)n_hyp * nb * NS);
+    a_sums.alloc((size_t)n_hyp * NS);
+    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_pts * 12, hipMemcpyHostToDevice, h->stream));
+    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_pts * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const QueryDev d{q_pw.p, q_tab.p, q_bound.p, q_best.p, q_obj.p, q_dist.p, nullptr};
+    const std::function<void(const QueryChunk&)> winner = [&](const QueryChunk& c) {
+        HIP_TRY(launch_align_winner(h->s_out.p, h->q_row_meta.p, c.n_rows, q_tab.p, (int)n_obj, n_rows, q_best.p, a_grad.p, h->stream));
+    };
+    align_loop(hyp, prm, trace, &h->a_stats[4],
+               [&](const std::vector<float>& hyp_tab, std::vector<double>& sums) {
+                   HIP_TRY(hipMemcpyAsync(a_hyp.p, hyp_tab.data(), hyp_tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+                   HIP_TRY(launch_align_transform(a_pts.p, n_pts, a_hyp.p, 0, n_rows, q_pw.p, h->stream));
+                   query_core(h, codes, n_obj, n_rows, d, true, plan, timer, h->a_stats, winner);
+                   HIP_TRY(launch_align_gram(q_pw.p, q_obj.p, q_dist.p, a_grad.p, weights ? a_w.p : nullptr, n_pts, (int)n_hyp, a_hyp.p, prm.huber,
+                                             prm.max_dist, a_slab.p, a_sums.p, h->stream));
+                   HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+                   HIP_TRY(hipStreamSynchronize(h->stream));    // the sums; `plan` and hyp_tab have been consumed
+               },
+               [&](int64_t k) {
+                   if (!obj) return;
+                   HIP_TRY(hipMemcpyAsync(r_obj.p + k * n_pts, q_obj.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
+                   HIP_TRY(hipMemcpyAsync(r_dist.p + k * n_pts, q_dist.p + k * n_pts, (size_t)n_pts * 4, hipMemcpyDeviceToDevice, h->stream));
+               });
     if (obj) {
         HIP_TRY(hipMemcpyAsync(obj, r_obj.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(dist, r_dist.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+    for (int64_t k = 0; k < n_hyp; ++k) align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
+}
+
+// ------------------------------------------------------------------------------------------------
+// ray alignment (dsp_map_align_rays; arithmetic: align_rays_math.h, kernels: align_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// the default gate on the along-ray gap in units of max_dist (profiles/map_align_rays.md: the sweep behind it)
+constexpr double ALIGN_RAYS_GAP_FACTOR = 2.0;
+
+// what dsp_map_align_rays refuses before it touches the device, besides the map: nullptr, or what is wrong
+const char* align_rays_check_inputs(const dsp_align_params& p, const dsp_raycast_params& rp, double max_gap, const double* T0, int64_t n_hyp,
+                                    const float* weights, int64_t n_rays, int64_t n_obj) {
+    if (const char* why = align_check_inputs(p, T0, n_hyp, weights, n_rays)) return why;
+    if (const char* why = raycast_check_host(rp.t_min, rp.t_max, rp.eps, rp.relax, rp.max_steps)) return why;
+    if (const char* why = align_rays_check_gap_host(max_gap, p.max_dist)) return why;
+    return raycast_check_size(n_obj, n_hyp * n_rays);
+}
+
+// Rays and weights are uploaded once; per evaluation the host sends the hypotheses' fp32 poses and reads the cast's pair counts, live polls
+// and winner counts and align_math::NSUM doubles per hypothesis.  The rows r = h n_rays + i of all hypotheses are ONE cast.
+void align_rays_run(dsp_handle* h, const std::vector<float>& tab, const float* codes, int64_t n_obj, const float* pts, const float* origins,
+                    const float* weights, int64_t n_rays, const double* T0, int64_t n_hyp, const dsp_align_params& prm, const raycast_math::Params& rprm,
+                    double max_gap, double* T_out, double* record, int32_t* obj, float* dist, float* t_hit, int32_t* status, double* trace) {
+    constexpr int NS = align_math::NSUM;
+    for (auto& c : h->ar_stats) c = 0;
+    std::vector<AlignHyp> hyp = align_start(T0, n_hyp);
+    if (trace) std::fill(trace, trace + (size_t)n_hyp * prm.iterations * DSP_ALIGN_TRACE, 0.0);
+    if (n_hyp == 0) return;
+    if (n_rays == 0 || n_obj == 0) {
+        align_write_no_support(hyp, prm, T_out, record);
+        if (obj)
+            for (int64_t r = 0; r < n_hyp * n_rays; ++r) { obj[r] = -1; dist[r] = t_hit[r] = INFINITY; status[r] = raycast_math::STATUS_MISS; }
+        return;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_rows = n_hyp * n_rays, nb = align_gram_blocks(n_rays);
+    DevBuf<float> a_pts, a_org, a_w, a_hyp, a_grad, c_tab, c_cb, c_pw, c_ow, c_dir, m_dist, r_dist, r_t;
+    DevBuf<int> m_obj, r_obj, r_status;
+    DevBuf<double> a_slab, a_sums;
+    RaycastWork w;
+    std::vector<float> cb;
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    cb = raycast_code_biases(h, codes, n_obj);
+    a_pts.alloc((size_t)n_rays * 3);
+    if (origins) a_org.alloc((size_t)n_rays * 3);
+    if (weights) a_w.alloc((size_t)n_rays);
+    a_hyp.alloc((size_t)n_hyp * ALIGN_HYP_STRIDE);
+    a_grad.alloc((size_t)n_rows * 3);
+    c_tab.alloc(tab.size());
+    c_cb.alloc(cb.size());
+    c_pw.alloc((size_t)n_rows * 3);
+    c_ow.alloc((size_t)n_rows * 3);
+    c_dir.alloc((size_t)n_rows * 3);
+    m_obj.alloc((size_t)n_rows);
+    m_dist.alloc((size_t)n_rows);
+    if (obj) { r_obj.alloc((size_t)n_rows); r_dist.alloc((size_t)n_rows); r_t.alloc((size_t)n_rows); r_status.alloc((size_t)n_rows); }
+    a_slab.alloc((size_t)n_hyp * nb * NS);
+    a_sums.alloc((size_t)n_hyp * NS);
+    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    if (origins) HIP_TRY(hipMemcpyAsync(a_org.p, origins, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_rays * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(c_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(c_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const RaycastRows gradient = [&](const RaycastDev&, const float* rows, const int2* row_meta, int n) {
+        HIP_TRY(launch_align_rays_gradient(rows, row_meta, n, c_tab.p, (int)n_obj, n_rows, a_grad.p, h->stream));
+    };
+    align_loop(hyp, prm, trace, &h->ar_stats[6],
+               [&](const std::vector<float>& hyp_tab, std::vector<double>& sums) {
+                   HIP_TRY(hipMemcpyAsync(a_hyp.p, hyp_tab.data(), hyp_tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+                   HIP_TRY(launch_align_rays_build(a_pts.p, origins ? a_org.p : nullptr, n_rays, a_hyp.p, n_rows, c_pw.p, c_ow.p, c_dir.p, h->stream));
+                   raycast_core(h, w, c_ow.p, c_dir.p, c_tab.p, c_cb.p, n_obj, n_rows, rprm, nullptr, timer, h->ar_stats, gradient);
+                   HIP_TRY(launch_align_rays_residual(c_ow.p, c_dir.p, w.r_obj.p, w.r_t.p, w.r_dist.p, w.r_status.p, a_grad.p, n_rows, max_gap, m_obj.p,
+                                                      m_dist.p, h->stream));
+                   HIP_TRY(launch_align_gram(c_pw.p, m_obj.p, m_dist.p, a_grad.p, weights ? a_w.p : nullptr, n_rays, (int)n_hyp, a_hyp.p, prm.huber,
+                                             prm.max_dist, a_slab.p, a_sums.p, h->stream));
+                   HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+                   HIP_TRY(hipStreamSynchronize(h->stream));    // the sums; w's uploads and hyp_tab have been consumed
+                   raycast_core_stats(w, h->ar_stats);
+               },
+               [&](int64_t k) {
+                   if (!obj) return;
+                   const size_t o = (size_t)k * n_rays, nbytes = (size_t)n_rays * 4;
+                   HIP_TRY(hipMemcpyAsync(r_obj.p + o, m_obj.p + o, nbytes, hipMemcpyDeviceToDevice, h->stream));
+                   HIP_TRY(hipMemcpyAsync(r_dist.p + o, m_dist.p + o, nbytes, hipMemcpyDeviceToDevice, h->stream));
+                   HIP_TRY(hipMemcpyAsync(r_t.p + o, w.r_t.p + o, nbytes, hipMemcpyDeviceToDevice, h->stream));
+                   HIP_TRY(hipMemcpyAsync(r_status.p + o, w.r_status.p + o, nbytes, hipMemcpyDeviceToDevice, h->stream));
+               });
+    if (obj) {
+        HIP_TRY(hipMemcpyAsync(obj, r_obj.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(dist, r_dist.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(t_hit, r_t.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(status, r_status.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, h->stream));
     }
     timer.mark();
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -730,6 +905,55 @@ int dsp_map_align(dsp_handle* h, const float* t_world_obj, const float* codes, i
         const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
         align_run(h, tab, codes, n_obj, pts_sensor, weights, n_pts, t_world_sensor0, n_hyp, *params, t_world_sensor, record, obj, dist, trace);
     });
+}
+
+double dsp_align_rays_default_max_gap(const dsp_align_params* params) { return params ? ALIGN_RAYS_GAP_FACTOR * params->max_dist : 0.0; }
+
+int dsp_map_align_rays(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_sensor, const float* origins_sensor,
+                       const float* weights, int64_t n_rays, const double* t_world_sensor0, int64_t n_hyp, const dsp_align_params* params,
+                       const dsp_raycast_params* raycast, double max_gap, double* t_world_sensor, double* record, int32_t* obj, float* dist, float* t_hit,
+                       int32_t* status, double* trace) {
+    if (!h || !params || !raycast || n_obj < 0 || n_rays < 0 || n_hyp < 0) return DSP_E_ARG;
+    const int n_out = (obj != nullptr) + (dist != nullptr) + (t_hit != nullptr) + (status != nullptr);
+    if (n_out != 0 && n_out != 4) return DSP_E_ARG;
+    if ((n_obj > 0 && (!t_world_obj || !codes)) || (n_rays > 0 && !pts_sensor) || (n_hyp > 0 && (!t_world_sensor0 || !t_world_sensor || !record)))
+        return DSP_E_ARG;
+    return guarded(h, [&] {
+        if (const char* why = align_rays_check_inputs(*params, *raycast, max_gap, t_world_sensor0, n_hyp, weights, n_rays, n_obj))
+            throw std::invalid_argument(why);
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        align_rays_run(h, tab, codes, n_obj, pts_sensor, origins_sensor, weights, n_rays, t_world_sensor0, n_hyp, *params, raycast_params(*raycast), max_gap,
+                       t_world_sensor, record, obj, dist, t_hit, status, trace);
+    });
+}
+
+int dsp_map_align_rays_last_stats(dsp_handle* h, int64_t* counts7) {
+    if (!h || !counts7) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts7, h->ar_stats, sizeof h->ar_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_align_rays_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const double* t_world_sensor0,
+                               int64_t n_hyp, const float* weights, int64_t n_rays, int64_t n_obj) {
+    if (!params || !raycast || n_hyp < 0 || n_rays < 0 || n_obj < 0 || (n_hyp > 0 && !t_world_sensor0)) return DSP_E_ARG;
+    if (n_obj > QUERY_MAX_OBJ) return DSP_E_ARG;
+    return align_rays_check_inputs(*params, *raycast, max_gap, t_world_sensor0, n_hyp, weights, n_rays, n_obj) ? DSP_E_ARG : DSP_OK;
+}
+
+int dsp_debug_align_ray_rows(int64_t n, const float* origins_world, const float* pts_world, const int32_t* obj, const float* t_hit, const float* dist_hit,
+                             const int32_t* status, const float* grad_world, const float* weights, double huber, double max_dist, double max_gap,
+                             int32_t* obj_row, float* d, double* sums30) {
+    if (n < 0 || !sums30 || (n > 0 && (!origins_world || !pts_world || !obj || !t_hit || !dist_hit || !status || !grad_world || !obj_row || !d)))
+        return DSP_E_ARG;
+    if (!std::isfinite(max_dist) || !std::isfinite(huber) || !(huber > 0.0) || !(huber <= max_dist)) return DSP_E_ARG;
+    if (align_rays_check_gap_host(max_gap, max_dist)) return DSP_E_ARG;
+    try {
+        align_ray_rows_host(n, origins_world, pts_world, obj, t_hit, dist_hit, status, grad_world, weights, huber, max_dist, max_gap, obj_row, d, sums30);
+    } catch (const std::bad_alloc&) {
+        return DSP_E_NOMEM;
+    }
+    return DSP_OK;
 }
 
 int dsp_map_align_last_stats(dsp_handle* h, int64_t* counts5) {

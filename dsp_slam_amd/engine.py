@@ -971,14 +971,20 @@ class Engine(object):
         L.check(L.load().dsp_map_align(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), L.ptr(w), n, L.ptr(t0, L.c_f64p), n_hyp, C.byref(prm),
                                        L.ptr(pose, L.c_f64p), L.ptr(rec, L.c_f64p), L.ptr(obj, L.c_i32p), L.ptr(dist), L.ptr(tr, L.c_f64p)),
                 self._h, "dsp_map_align")
+        out = self._align_result(pose, rec, tr, prm, n_hyp, iters)
+        if per_point:
+            out["obj"], out["dist"] = obj, dist
+        return out
+
+    @staticmethod
+    def _align_result(pose, rec, tr, prm, n_hyp, iters):
+        """the result dict of align_to_map / align_rays_to_map from the call's record and trace arrays"""
         out = {"pose": pose, "status": rec[:, 0].astype(np.int32), "evaluations": rec[:, 1].astype(np.int32), "steps": rec[:, 2].astype(np.int32),
                "cost0": rec[:, 3].copy(), "cost": rec[:, 4].copy(), "n_used": rec[:, 5].astype(np.int64), "sum_w": rec[:, 6].copy(),
                "lambda": rec[:, 7].copy(), "information": rec[:, 8:44].reshape(n_hyp, 6, 6).copy(), "b": rec[:, 44:50].copy()}
         ok = np.flatnonzero(out["n_used"] >= prm.min_points)
         out["best"] = int(ok[np.argmin(out["cost"][ok])]) if ok.size else -1
-        if per_point:
-            out["obj"], out["dist"] = obj, dist
-        if trace:
+        if tr is not None:
             iu = np.triu_indices(6)
             hh = np.zeros((n_hyp, iters, 6, 6), np.float64)
             hh[:, :, iu[0], iu[1]] = tr[:, :, 20:41]
@@ -993,6 +999,61 @@ class Engine(object):
         c = np.zeros(5, np.int64)
         L.check(L.load().dsp_map_align_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_align_last_stats")
         return {"rows": int(c[0]), "tiles": int(c[1]), "chunks": int(c[2]), "passes": int(c[3]), "evaluations": int(c[4])}
+
+    # -- ray alignment ------------------------------------------------------------------------------
+    def align_rays_to_map(self, t_world_obj, codes, pts_sensor, t_world_sensor0, origins=None, weights=None, trace=False, per_ray=False,
+                          max_gap=None, raycast=None, **params):
+        """Where is the sensor, given the depths it measured along its rays?  Projective SE(3) Gauss-Newton against the ray-cast map
+        (dsp_map_align_rays).  pts_sensor: (n_rays, 3) measured end points in the sensor frame; origins: None (the sensor origin) or
+        (n_rays, 3); the ray of an observation runs from its origin through its end point.  max_gap: the gate on |observed depth - cast
+        depth| (None: the library's default, 2 max_dist; inf: no gate); raycast: a dict of raycast_params fields; everything else as
+        align_to_map.  The dict of align_to_map; with per_ray=True `obj` (the matched object, -1 for unmatched), `dist` (the first-order
+        signed distance), `t` and `status_ray` (the cast's hit parameter and L.RAYCAST_* status), (n_hyp, n_rays) each, at the returned state."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        pts = L.f32(np.asarray(pts_sensor, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        org = None
+        if origins is not None:
+            org = L.f32(np.asarray(origins, np.float32).reshape(-1, 3))
+            if org.shape[0] != n:
+                raise ValueError("one origin per point")
+        w = None
+        if weights is not None:
+            w = L.f32(np.asarray(weights, np.float32).reshape(-1))
+            if w.shape[0] != n:
+                raise ValueError("one weight per ray")
+        t0 = np.ascontiguousarray(np.asarray(t_world_sensor0, np.float64).reshape(-1, 4, 4))
+        n_hyp = t0.shape[0]
+        prm = self.align_params(**params)
+        rprm = self.raycast_params(**(raycast or {}))
+        lib = L.load()
+        gap = float(lib.dsp_align_rays_default_max_gap(C.byref(prm))) if max_gap is None else float(max_gap)
+        iters = max(int(prm.iterations), 0)
+        pose, rec = np.zeros((n_hyp, 4, 4), np.float64), np.zeros((n_hyp, L.ALIGN_RECORD), np.float64)
+        obj = np.zeros((n_hyp, n), np.int32) if per_ray else None
+        dist = np.zeros((n_hyp, n), np.float32) if per_ray else None
+        th = np.zeros((n_hyp, n), np.float32) if per_ray else None
+        st = np.zeros((n_hyp, n), np.int32) if per_ray else None
+        tr = np.zeros((n_hyp, iters, L.ALIGN_TRACE), np.float64) if trace else None
+        L.check(lib.dsp_map_align_rays(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), L.ptr(org), L.ptr(w), n, L.ptr(t0, L.c_f64p), n_hyp,
+                                       C.byref(prm), C.byref(rprm), gap, L.ptr(pose, L.c_f64p), L.ptr(rec, L.c_f64p), L.ptr(obj, L.c_i32p), L.ptr(dist),
+                                       L.ptr(th), L.ptr(st, L.c_i32p), L.ptr(tr, L.c_f64p)), self._h, "dsp_map_align_rays")
+        out = self._align_result(pose, rec, tr, prm, n_hyp, iters)
+        out["max_gap"] = gap
+        if per_ray:
+            out["obj"], out["dist"], out["t"], out["status_ray"] = obj, dist, th, st
+        return out
+
+    def align_rays_stats(self):
+        """Counts of the last align_rays_to_map on this engine (dsp_map_align_rays_last_stats): the cast's, summed over its evaluations."""
+        c = np.zeros(7, np.int64)
+        L.check(L.load().dsp_map_align_rays_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_align_rays_last_stats")
+        return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5]),
+                "evaluations": int(c[6])}
 
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""

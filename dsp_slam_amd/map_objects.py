@@ -107,6 +107,46 @@ def render(engine, objects, K, t_world_cam, width, height, normals=False, **para
     return out
 
 
+def localise_rays(engine, objects, pts_sensor, t_world_sensor0, origins=None, weights=None, trace=False, **params):
+    """Engine.align_rays_to_map on the list read_map_objects returns: the sensor-to-world pose at which the map, cast along the sensor's
+    rays, shows the measured depths.  The result dict of Engine.align_rays_to_map with the per-ray outputs at every returned pose, plus
+    `id`: the map's object id per hypothesis and ray, -1 where the ray is unmatched.  params: max_gap, raycast={...} and the fields of
+    Engine.align_params."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    res = engine.align_rays_to_map(poses, [o["code"] for o in objects], pts_sensor, t_world_sensor0, origins=origins, weights=weights, trace=trace,
+                                   per_ray=True, **params)
+    return with_ids(res, [o["id"] for o in objects])
+
+
+def backproject_depth(depth, K):
+    """The camera-frame points of a z-depth image by the pixel_rays convention: pixel (column j, row i) with depth z is
+    z * ((j - cx) / fx, (i - cy) / fy, 1).  -> points (n, 3) float32 and their flat pixel indices (n,), row-major; pixels whose depth is
+    not finite or not positive are skipped."""
+    depth = np.asarray(depth, np.float64)
+    K = np.asarray(K, np.float64)
+    fx, fy, cx, cy = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.reshape(4)
+    height, width = depth.shape
+    j, i = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    z = depth.reshape(-1)
+    with np.errstate(invalid="ignore"):
+        keep = np.flatnonzero(np.isfinite(z) & (z > 0))
+    d_cam = np.stack([(j - cx) / fx, (i - cy) / fy, np.ones_like(j)], -1).reshape(-1, 3)
+    return (d_cam[keep] * z[keep, None]).astype(np.float32), keep
+
+
+def localise_depth(engine, objects, depth, K, t_world_cam0, weights=None, trace=False, **params):
+    """localise_rays on a z-depth image (height, width) of a pinhole camera: every pixel with a finite positive depth is one ray from the
+    camera centre (backproject_depth; the convention of pixel_rays and render, so render(...)["depth"] fed back at the rendering pose
+    costs about nothing there).  weights: None or an image.  The result of localise_rays plus `pixel`: the flat row-major pixel index of
+    every ray."""
+    pts, keep = backproject_depth(depth, K)
+    w = None if weights is None else np.asarray(weights, np.float32).reshape(-1)[keep]
+    res = localise_rays(engine, objects, pts, t_world_cam0, weights=w, trace=trace, **params)
+    res["pixel"] = keep
+    return res
+
+
 def with_ids(result, ids):
     """result (an Engine.query_map dict) with `id` added: ids[obj] per point, -1 where obj is -1."""
     out = dict(result)

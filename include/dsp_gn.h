@@ -467,6 +467,51 @@ int dsp_debug_align_rows(int64_t n, const float* pts_world, const int32_t* obj, 
 int dsp_debug_align_step(const double* H36, const double* b6, double damp, double lambda, const double* t16, int32_t* status, double* xi6,
                          double* t_trial16);
 
+/* ---- ray alignment: where is the sensor, given the depths it measured along its rays?  Projective Gauss-Newton against the cast map ----
+ * dsp_map_align answers for a cloud already cut down to object points, and pairs a point with the nearest surface among the unit spheres
+ * that contain it: a point outside every sphere has no residual, occlusion between objects is ignored, and a pose that puts a map object
+ * between the sensor and what it measured costs nothing.  dsp_map_align_rays pairs every observation with the surface its RAY sees.
+ * Observation i is the measured end point pts_sensor[i] of the ray that runs from origins_sensor[i] (NULL: the sensor origin 0 0 0)
+ * through it, both in the sensor frame.  The map, the hypotheses, weights, record, trace, statuses, loop, step control, convergence rule
+ * and step are dsp_map_align's; hypotheses are independent, byte for byte, and one that has ended costs no decoder rows.
+ * One evaluation of a hypothesis at pose T (csrc/align_rays_math.h, one correctly rounded fp32 operation at a time):
+ *   p_w = T p_s, o_w = T o_s as dsp_map_align transforms points; dir = p_w - o_w; u = dir / |dir|, len = |dir| is the observed depth.  A
+ *   ray with a number that is not finite or with p_s == o_s is void.
+ *   The rays (o_w, dir) of ALL live hypotheses go through dsp_map_raycast's pipeline in one cast with `raycast`: obj, t_hit, the hit
+ *   sample's dist_hit = sdf s and the status per ray; the winners' hit samples go through the decoder's jacobian form, and g_w is the
+ *   gradient rotated to the world and multiplied by s (NOT normalised).
+ *   gap = len - t_hit;  d = fmaf(g_w . u, gap, dist_hit): the first-order signed distance from the measured point to the surface patch its
+ *   ray sees.  It removes the marcher's eps staircase to first order; a residual pose error of second order in eps and gap remains (about
+ *   half of eps in translation on the project's test scene: profiles/map_align_rays.md), so cast with a smaller eps for a finer pose.
+ *   The observation is matched when status == DSP_RAYCAST_HIT (UNDECIDED is not), gap is finite and |gap| <= max_gap (compared in fp64).
+ *   A matched observation enters dsp_map_align's rows with (p_w, obj, d, g_w): J = [g_w, p_w x g_w], because the measured point moves with
+ *   the sensor and the patch stays.  An unmatched one whose p_w is finite and whose weight is > 0 contributes w rho(max_dist), like a
+ *   valid point that is not used: seeing through a map object, or at a surface far from the measured depth, costs something.
+ * max_gap >= max_dist, not NaN; +inf = no gate.  Without the gate, background rays reach the system through grazing hits, where
+ * g_w . u -> 0 makes d small whatever the depth mismatch.  dsp_align_rays_default_max_gap: 2 max_dist (the sweep in the profile).
+ * Outputs as dsp_map_align's, and per observation at the RETURNED state (optional, all four or none, n_hyp x n_rays): obj (the matched
+ * object, -1 for unmatched), dist (d; +inf without a winner), t_hit and status of the cast.  With no rays or no objects every hypothesis
+ * returns DSP_ALIGN_NO_SUPPORT with its input pose (-1, +inf, +inf, MISS).  DSP_E_ARG, before the device is touched: everything
+ * dsp_map_align and dsp_map_raycast refuse; max_gap < max_dist or NaN; n_hyp x n_rays > 2^31 - 1; n_obj x ceil(n_hyp n_rays / 64) pair
+ * counts or the objects' code biases beyond dsp_map_raycast's budgets ("split the request": hypotheses are not grouped). */
+double dsp_align_rays_default_max_gap(const dsp_align_params* params);
+int dsp_map_align_rays(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_sensor, const float* origins_sensor,
+                       const float* weights, int64_t n_rays, const double* t_world_sensor0, int64_t n_hyp, const dsp_align_params* params,
+                       const dsp_raycast_params* raycast, double max_gap, double* t_world_sensor, double* record, int32_t* obj, float* dist, float* t_hit,
+                       int32_t* status, double* trace);
+/* Counts of the last dsp_map_align_rays on this handle: counts7 = dsp_map_raycast_last_stats' six summed over its evaluations (pairs,
+ * decoder rows of the march, tiles, rounds, passes, exhausted pairs), device evaluations. */
+int dsp_map_align_rays_last_stats(dsp_handle* h, int64_t* counts7);
+/* Host only, no handle: csrc/align_rays_math.h on arrays.  dsp_debug_align_ray_rows: n rays' o_w and p_w (n x 3 each), the cast's answers
+ * (obj, t_hit, dist_hit, status), g_w (n x 3, read where obj >= 0), w (NULL = ones) and the three gates -> obj_row, d (n each) and sums30
+ * as dsp_debug_align_rows.  dsp_debug_align_rays_check: DSP_E_ARG for what dsp_map_align_rays refuses before it touches the device, the
+ * map's poses and codes excepted (n_obj objects are assumed valid). */
+int dsp_debug_align_ray_rows(int64_t n, const float* origins_world, const float* pts_world, const int32_t* obj, const float* t_hit, const float* dist_hit,
+                             const int32_t* status, const float* grad_world, const float* weights, double huber, double max_dist, double max_gap,
+                             int32_t* obj_row, float* d, double* sums30);
+int dsp_debug_align_rays_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const double* t_world_sensor0,
+                               int64_t n_hyp, const float* weights, int64_t n_rays, int64_t n_obj);
+
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,

@@ -197,6 +197,12 @@ SYMBOLS = [
                                            c_i32p, c_f32p, c_f64p]),
     ("dsp_debug_align_rays_check", C.c_int, [C.POINTER(AlignParams), C.POINTER(RaycastParams), C.c_double, c_f64p, C.c_int64, c_f32p, C.c_int64,
                                              C.c_int64]),
+    ("dsp_map_align_objects", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(AlignParams),
+                                        C.POINTER(RaycastParams), C.c_double, c_f32p, c_f64p, c_f64p, c_i32p, c_f32p, c_f32p, c_i32p, c_f64p]),
+    ("dsp_map_align_objects_last_stats", C.c_int, [_VP, c_i64p]),
+    ("dsp_debug_align_objects_rows", C.c_int, [C.c_int64, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_double, C.c_double, c_f64p]),
+    ("dsp_debug_align_objects_compose", C.c_int, [C.c_int64, c_f64p, c_f32p, c_f32p]),
+    ("dsp_debug_align_objects_check", C.c_int, [C.POINTER(AlignParams), C.POINTER(RaycastParams), C.c_double, c_f32p, c_f32p, C.c_int64, C.c_int64]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

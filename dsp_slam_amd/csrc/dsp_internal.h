@@ -640,4 +640,20 @@ double align_cost_host(const double* sums, double huber, double max_dist);
 bool align_solve_host(const double* H36, const double* b6, double damp, double lambda, double* xi6);
 void align_apply_step_host(const double* xi6, const double* t_in, double* t_out);
 
+// ---- object refinement (align_objects_kernels.hip; the arithmetic: align_objects_math.h) ---------
+// Behind a cast's winner count (launch_raycast_wincount: wave_base = the scan per (object, wave), totals on the host).  list: win_ray[off[k] + j]
+// <- the j-th winner of object k in ascending ray order; off = the exclusive scan of the totals (n_obj ints), n_list their sum.  gram: blocks[q] =
+// {object, first list position, positions <= align_math::BLOCK, 0} -> slab[q][NSUM]; then sums[k][NSUM] <- the slabs [first[k], first[k + 1]) in
+// ascending order, zero where there is none (first: n_obj + 1 ints).  obj_row / d_row / grad_w are per ray (launch_align_rays_residual / _gradient).
+hipError_t launch_align_objects_list(const int* obj, int n_rays, int n_obj, int n_waves, const int* wave_base, const int* off, int n_list, int* win_ray,
+                                     hipStream_t s);
+hipError_t launch_align_objects_gram(const int4* blocks, int n_blocks, const int* first, int n_obj, const int* win_ray, int n_list, int n_rays,
+                                     const float* pts_w, const int* obj_row, const float* d_row, const float* grad_w, const float* weights, double huber,
+                                     double max_dist, double* slab, double* sums, hipStream_t s);
+// align_objects_math.h compiled for the host in the translation unit that has contraction off (dsp_map_align_objects, dsp_debug_align_objects_*)
+void align_objects_compose_host(const double* c16, const float* t16, float* out16);
+void align_objects_directions_host(int64_t n, const float* org_w, const float* pts_w, float* dir_w);
+void align_objects_rows_host(int64_t n, const float* pts_w, const int32_t* winner, const int32_t* obj_row, const float* d_row, const float* grad_w,
+                             const float* weights, int64_t n_obj, double huber, double max_dist, double* sums);
+
 }  // namespace dsp

@@ -1,6 +1,7 @@
 // The object map on the host: signed distance and normal of world points (dsp_map_query) and the alignment of a point cloud to the map
 // (dsp_map_align), which runs the query's core; ray casting (dsp_map_raycast) and the alignment of depth rays to the map
-// (dsp_map_align_rays), which runs the cast's core inside the alignment's hypothesis loop; with their C ABI.
+// (dsp_map_align_rays), which runs the cast's core inside the alignment's hypothesis loop; the refinement of the objects' own poses against
+// world-frame depth rays (dsp_map_align_objects), which runs the same loop with one correction per object; with their C ABI.
 #include "decoder_calls.h"
 #include "decoder_pack.h"
 #include "query_math.h"     // constants only: the arithmetic is compiled in query_kernels.hip (contraction off)
@@ -580,8 +581,9 @@ void align_write_no_support(std::vector<AlignHyp>& hyp, const dsp_align_params& 
 
 // The hypothesis loop of dsp_map_align and dsp_map_align_rays: statuses, step control, convergence rule, Cholesky and exp_se3; the step lives
 // on the host.  evaluate(hyp_tab, sums) runs one evaluation of every live hypothesis at the fp32 poses of hyp_tab (ALIGN_HYP_STRIDE floats
-// per hypothesis; it uploads them) and returns with align_math::NSUM sums per hypothesis on the host and the stream idle.  accepted(k) is
-// called when hypothesis k's evaluation becomes its returned state.  *n_evals += 1 per evaluation.
+// per hypothesis; it uploads them) and returns with align_math::NSUM sums per hypothesis on the host and the stream idle; it may end a
+// hypothesis itself (live = false and a status: dsp_map_align_objects, whose trial pose the map may refuse), which is then skipped.
+// accepted(k) (may be empty) is called when hypothesis k's evaluation becomes its returned state.  *n_evals += 1 per evaluation.
 void align_loop(std::vector<AlignHyp>& hyp, const dsp_align_params& prm, double* trace, int64_t* n_evals,
                 const std::function<void(const std::vector<float>&, std::vector<double>&)>& evaluate, const std::function<void(int64_t)>& accepted) {
     constexpr int NS = align_math::NSUM;
@@ -825,6 +827,170 @@ void align_rays_run(dsp_handle* h, const std::vector<float>& tab, const float* c
     for (int64_t k = 0; k < n_hyp; ++k) align_write(hyp[k], T_out + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
 }
 
+// ------------------------------------------------------------------------------------------------
+// object refinement (dsp_map_align_objects; arithmetic: align_objects_math.h, kernels: align_objects_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// what dsp_map_align_objects refuses before it touches the device, besides the map: nullptr, or what is wrong
+const char* align_objects_check_inputs(const dsp_align_params& p, const dsp_raycast_params& rp, double max_gap, const float* origins, const float* weights,
+                                       int64_t n_rays, int64_t n_obj) {
+    if (const char* why = align_check_params(p)) return why;
+    if (n_rays > (int64_t)0x7fffffff) return "align_objects: n_rays exceeds 2^31 - 1 (split the request)";
+    if (n_rays > 0 && !origins) return "align_objects: origins_world is required (one ray origin per measured point)";
+    if (weights)
+        for (int64_t i = 0; i < n_rays; ++i)
+            if (!(weights[i] >= 0.f) || !std::isfinite(weights[i])) return "align: weights must be finite and >= 0";
+    if (const char* why = raycast_check_host(rp.t_min, rp.t_max, rp.eps, rp.relax, rp.max_steps)) return why;
+    if (const char* why = align_rays_check_gap_host(max_gap, p.max_dist)) return why;
+    return raycast_check_size(n_obj, n_rays);
+}
+
+// Rays, directions and weights are uploaded once; per evaluation the host sends the object table of the composed poses and reads the cast's
+// pair counts, live polls and winner counts -- from which it makes the lists' offsets and the block table -- and align_math::NSUM doubles
+// per object.  The "hypotheses" of align_loop are the objects and their poses the corrections C_k.
+void align_objects_run(dsp_handle* h, const std::vector<float>& tab0, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts,
+                       const float* origins, const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params& prm,
+                       const raycast_math::Params& rprm, double max_gap, float* t_out, double* correction, double* record, int32_t* obj, float* dist,
+                       float* t_hit, int32_t* status, double* trace) {
+    constexpr int NS = align_math::NSUM;
+    for (auto& c : h->ao_stats) c = 0;
+    if (trace) std::fill(trace, trace + (size_t)n_obj * prm.iterations * DSP_ALIGN_TRACE, 0.0);
+    auto no_rays = [&] {
+        if (obj)
+            for (int64_t r = 0; r < n_rays; ++r) { obj[r] = -1; dist[r] = t_hit[r] = INFINITY; status[r] = raycast_math::STATUS_MISS; }
+    };
+    if (n_obj == 0) { no_rays(); return; }
+    std::vector<double> ident((size_t)n_obj * 16, 0.0);
+    for (int64_t k = 0; k < n_obj; ++k) ident[16 * k] = ident[16 * k + 5] = ident[16 * k + 10] = ident[16 * k + 15] = 1.0;
+    std::vector<AlignHyp> hyp = align_start(ident.data(), n_obj);
+    const double zero[NS] = {};
+    for (int64_t k = 0; k < n_obj; ++k) {
+        hyp[k].F0 = hyp[k].F_acc = align_cost_host(zero, prm.huber, prm.max_dist);
+        if (refine && !refine[k]) hyp[k].live = false;                  // never evaluated: status OK, 0 evaluations
+        else if (n_rays == 0) { hyp[k].live = false; hyp[k].status = DSP_ALIGN_NO_SUPPORT; }
+    }
+    auto write_out = [&] {
+        for (int64_t k = 0; k < n_obj; ++k) {
+            align_write(hyp[k], correction + 16 * k, record + (size_t)DSP_ALIGN_RECORD * k);
+            align_objects_compose_host(hyp[k].T_acc, t_world_obj + 16 * k, t_out + 16 * k);
+        }
+    };
+    bool any = false;
+    for (const AlignHyp& a : hyp) any = any || a.live;
+    if (n_rays == 0 || (!any && !obj)) { no_rays(); write_out(); return; }
+    HIP_TRY(hipSetDevice(h->device));
+    DevBuf<float> a_pts, a_org, a_dir, a_w, a_grad, c_tab, c_cb, m_dist;
+    DevBuf<int> m_obj, a_off, a_first, a_win;
+    DevBuf<int4> a_blocks;
+    DevBuf<double> a_slab, a_sums;
+    RaycastWork w;
+    std::vector<float> cb, dirs((size_t)n_rays * 3), tab((size_t)n_obj * query_math::OBJ_STRIDE, 0.f);
+    std::vector<int> off((size_t)n_obj), first((size_t)n_obj + 1);
+    std::vector<int4> blocks;
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    cb = raycast_code_biases(h, codes, n_obj);
+    align_objects_directions_host(n_rays, origins, pts, dirs.data());
+    a_pts.alloc((size_t)n_rays * 3);
+    a_org.alloc((size_t)n_rays * 3);
+    a_dir.alloc((size_t)n_rays * 3);
+    if (weights) a_w.alloc((size_t)n_rays);
+    a_grad.alloc((size_t)n_rays * 3);
+    c_tab.alloc(tab.size());
+    c_cb.alloc(cb.size());
+    m_obj.alloc((size_t)n_rays);
+    m_dist.alloc((size_t)n_rays);
+    a_off.alloc((size_t)n_obj);
+    a_first.alloc((size_t)n_obj + 1);
+    a_win.alloc((size_t)n_rays);
+    a_sums.alloc((size_t)n_obj * NS);
+    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_org.p, origins, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_dir.p, dirs.data(), (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_rays * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(c_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const RaycastRows gradient = [&](const RaycastDev&, const float* rows, const int2* row_meta, int n) {
+        HIP_TRY(launch_align_rays_gradient(rows, row_meta, n, c_tab.p, (int)n_obj, n_rays, a_grad.p, h->stream));
+    };
+    // the object table at the trial poses of the evaluated objects (trial) or at every object's accepted pose; a trial pose the map's
+    // inversion refuses ends its object with SINGULAR at its accepted state
+    auto table = [&](bool trial) {
+        for (int64_t k = 0; k < n_obj; ++k) {
+            float pose[16];
+            float* e = tab.data() + k * query_math::OBJ_STRIDE;
+            bool ok = false;
+            if (trial && hyp[k].live) {
+                align_objects_compose_host(hyp[k].T_eval, t_world_obj + 16 * k, pose);
+                ok = query_invert_host(pose, e, e + 12);
+                if (!ok) { hyp[k].live = false; hyp[k].status = DSP_ALIGN_SINGULAR; }
+            }
+            if (!ok) {
+                align_objects_compose_host(hyp[k].T_acc, t_world_obj + 16 * k, pose);
+                if (!query_invert_host(pose, e, e + 12)) throw std::runtime_error("align_objects: an accepted pose is not invertible");
+            }
+            e[13] = std::isnan(tab0[(size_t)k * query_math::OBJ_STRIDE + 13]) ? std::nanf("") : e[12];     // a code that is not finite never wins
+        }
+    };
+    // table up, the cast with the winners' gradients behind it, the rows' (obj, d): the stream is NOT synchronised behind it
+    auto cast = [&](bool trial) {
+        table(trial);
+        HIP_TRY(hipMemcpyAsync(c_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+        raycast_core(h, w, a_org.p, a_dir.p, c_tab.p, c_cb.p, n_obj, n_rays, rprm, nullptr, timer, h->ao_stats, gradient);
+        HIP_TRY(launch_align_rays_residual(a_org.p, a_dir.p, w.r_obj.p, w.r_t.p, w.r_dist.p, w.r_status.p, a_grad.p, n_rays, max_gap, m_obj.p, m_dist.p,
+                                           h->stream));
+    };
+    align_loop(hyp, prm, trace, &h->ao_stats[6],
+               [&](const std::vector<float>&, std::vector<double>& sums) {
+                   cast(true);
+                   // w.cnt: the winners per object, read back by the cast.  The lists of ALL objects, blocks for the evaluated ones
+                   int64_t n_list = 0;
+                   blocks.clear();
+                   for (int64_t k = 0; k < n_obj; ++k) {
+                       off[k] = (int)n_list;
+                       first[k] = (int)blocks.size();
+                       if (hyp[k].live)
+                           for (int j = 0; j < w.cnt[k]; j += align_math::BLOCK)
+                               blocks.push_back(make_int4((int)k, (int)n_list + j, std::min(align_math::BLOCK, w.cnt[k] - j), 0));
+                       n_list += w.cnt[k];
+                   }
+                   first[n_obj] = (int)blocks.size();
+                   if (n_list > n_rays) throw std::runtime_error("align_objects: more winners than rays");
+                   a_blocks.ensure(blocks.size());
+                   a_slab.ensure(blocks.size() * NS);
+                   HIP_TRY(hipMemcpyAsync(a_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+                   HIP_TRY(hipMemcpyAsync(a_first.p, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+                   if (!blocks.empty())
+                       HIP_TRY(hipMemcpyAsync(a_blocks.p, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+                   HIP_TRY(launch_align_objects_list(w.r_obj.p, (int)n_rays, (int)n_obj, (int)((n_rays + 63) / 64), w.r_wave_cnt.p, a_off.p, (int)n_list,
+                                                     a_win.p, h->stream));
+                   HIP_TRY(launch_align_objects_gram(a_blocks.p, (int)blocks.size(), a_first.p, (int)n_obj, a_win.p, (int)n_list, (int)n_rays, a_pts.p,
+                                                     m_obj.p, m_dist.p, a_grad.p, weights ? a_w.p : nullptr, prm.huber, prm.max_dist, a_slab.p, a_sums.p,
+                                                     h->stream));
+                   HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+                   HIP_TRY(hipStreamSynchronize(h->stream));    // the sums; w's uploads, the table and the block table have been consumed
+                   raycast_core_stats(w, h->ao_stats);
+                   for (int64_t k = 0; k < n_obj; ++k)          // the object moves, not the measured point: b is row_terms's negated
+                       for (int q = 0; q < 6; ++q) sums[k * NS + align_math::IDX_B + q] = -sums[k * NS + align_math::IDX_B + q];
+               },
+               {});
+    if (obj) {      // one more evaluation of the returned map, every object at its returned pose
+        cast(false);
+        h->ao_stats[6] += 1;
+        HIP_TRY(hipMemcpyAsync(obj, m_obj.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(dist, m_dist.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(t_hit, w.r_t.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(status, w.r_status.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+    if (obj) raycast_core_stats(w, h->ao_stats);
+    write_out();
+}
+
 }  // namespace
 
 extern "C" {
@@ -953,6 +1119,53 @@ int dsp_debug_align_ray_rows(int64_t n, const float* origins_world, const float*
     } catch (const std::bad_alloc&) {
         return DSP_E_NOMEM;
     }
+    return DSP_OK;
+}
+
+int dsp_map_align_objects(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, const float* origins_world,
+                          const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params* params,
+                          const dsp_raycast_params* raycast, double max_gap, float* t_world_obj_out, double* correction, double* record, int32_t* obj,
+                          float* dist, float* t_hit, int32_t* status, double* trace) {
+    if (!h || !params || !raycast || n_obj < 0 || n_rays < 0) return DSP_E_ARG;
+    const int n_out = (obj != nullptr) + (dist != nullptr) + (t_hit != nullptr) + (status != nullptr);
+    if (n_out != 0 && n_out != 4) return DSP_E_ARG;
+    if ((n_obj > 0 && (!t_world_obj || !codes || !t_world_obj_out || !correction || !record)) || (n_rays > 0 && !pts_world)) return DSP_E_ARG;
+    return guarded(h, [&] {
+        if (const char* why = align_objects_check_inputs(*params, *raycast, max_gap, origins_world, weights, n_rays, n_obj)) throw std::invalid_argument(why);
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        align_objects_run(h, tab, t_world_obj, codes, n_obj, pts_world, origins_world, weights, n_rays, refine, *params, raycast_params(*raycast), max_gap,
+                          t_world_obj_out, correction, record, obj, dist, t_hit, status, trace);
+    });
+}
+
+int dsp_map_align_objects_last_stats(dsp_handle* h, int64_t* counts7) {
+    if (!h || !counts7) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts7, h->ao_stats, sizeof h->ao_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_align_objects_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const float* origins_world,
+                                  const float* weights, int64_t n_rays, int64_t n_obj) {
+    if (!params || !raycast || n_rays < 0 || n_obj < 0 || n_obj > QUERY_MAX_OBJ) return DSP_E_ARG;
+    return align_objects_check_inputs(*params, *raycast, max_gap, origins_world, weights, n_rays, n_obj) ? DSP_E_ARG : DSP_OK;
+}
+
+int dsp_debug_align_objects_rows(int64_t n, const float* pts_world, const int32_t* winner, const int32_t* obj_row, const float* d, const float* grad_world,
+                                 const float* weights, int64_t n_obj, double huber, double max_dist, double* sums) {
+    if (n < 0 || n_obj < 0 || (n_obj > 0 && !sums) || (n > 0 && (!pts_world || !winner || !obj_row || !d || !grad_world))) return DSP_E_ARG;
+    if (!std::isfinite(max_dist) || !std::isfinite(huber) || !(huber > 0.0) || !(huber <= max_dist)) return DSP_E_ARG;
+    try {
+        align_objects_rows_host(n, pts_world, winner, obj_row, d, grad_world, weights, n_obj, huber, max_dist, sums);
+    } catch (const std::bad_alloc&) {
+        return DSP_E_NOMEM;
+    }
+    return DSP_OK;
+}
+
+int dsp_debug_align_objects_compose(int64_t n, const double* correction, const float* t_world_obj, float* t_world_obj_out) {
+    if (n < 0 || (n > 0 && (!correction || !t_world_obj || !t_world_obj_out))) return DSP_E_ARG;
+    for (int64_t k = 0; k < n; ++k) align_objects_compose_host(correction + 16 * k, t_world_obj + 16 * k, t_world_obj_out + 16 * k);
     return DSP_OK;
 }
 

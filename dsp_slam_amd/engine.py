@@ -1055,6 +1055,68 @@ class Engine(object):
         return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5]),
                 "evaluations": int(c[6])}
 
+    # -- object refinement --------------------------------------------------------------------------
+    def align_objects_to_rays(self, t_world_obj, codes, pts_world, origins_world, weights=None, refine=None, trace=False, per_ray=False,
+                              max_gap=None, raycast=None, **params):
+        """Where are the objects, given depth rays from known sensor poses?  One SE(3) correction per map object, projective Gauss-Newton
+        against the ray-cast map (dsp_map_align_objects).  pts_world / origins_world: (n_rays, 3) measured end points and ray origins in
+        the WORLD frame (several frames are concatenated); refine: None (all) or (n_obj,) of 0 / 1, an object with 0 is never moved but
+        still occludes; max_gap, raycast, weights and params as align_rays_to_map.  The dict of align_to_map indexed by OBJECT (`pose` is
+        the correction C_k, `information` the 6 x 6 information of its left perturbation), plus `t_world_obj` (n_obj, 4, 4) float32, the
+        corrected poses C_k T_k0 (the input bytes where C_k is the identity), `correction` (n_obj, 4, 4) float64 and `max_gap`; with
+        per_ray=True `obj`, `dist`, `t`, `status_ray` (n_rays,) from one more evaluation of the returned map."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        pts = L.f32(np.asarray(pts_world, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        org = None
+        if origins_world is not None:
+            org = L.f32(np.asarray(origins_world, np.float32).reshape(-1, 3))
+            if org.shape[0] != n:
+                raise ValueError("one origin per point")
+        w = None
+        if weights is not None:
+            w = L.f32(np.asarray(weights, np.float32).reshape(-1))
+            if w.shape[0] != n:
+                raise ValueError("one weight per ray")
+        ref = None
+        if refine is not None:
+            ref = np.ascontiguousarray(np.asarray(refine).reshape(-1) != 0, np.uint8)
+            if ref.shape[0] != n_obj:
+                raise ValueError("one refine flag per object")
+        prm = self.align_params(**params)
+        rprm = self.raycast_params(**(raycast or {}))
+        lib = L.load()
+        gap = float(lib.dsp_align_rays_default_max_gap(C.byref(prm))) if max_gap is None else float(max_gap)
+        iters = max(int(prm.iterations), 0)
+        t_out, corr = np.zeros((n_obj, 4, 4), np.float32), np.zeros((n_obj, 4, 4), np.float64)
+        rec = np.zeros((n_obj, L.ALIGN_RECORD), np.float64)
+        obj = np.zeros(n, np.int32) if per_ray else None
+        dist = np.zeros(n, np.float32) if per_ray else None
+        th = np.zeros(n, np.float32) if per_ray else None
+        st = np.zeros(n, np.int32) if per_ray else None
+        tr = np.zeros((n_obj, iters, L.ALIGN_TRACE), np.float64) if trace else None
+        L.check(lib.dsp_map_align_objects(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), L.ptr(org), L.ptr(w), n, L.ptr(ref, C.POINTER(C.c_uint8)),
+                                          C.byref(prm), C.byref(rprm), gap, L.ptr(t_out), L.ptr(corr, L.c_f64p), L.ptr(rec, L.c_f64p),
+                                          L.ptr(obj, L.c_i32p), L.ptr(dist), L.ptr(th), L.ptr(st, L.c_i32p), L.ptr(tr, L.c_f64p)),
+                self._h, "dsp_map_align_objects")
+        out = self._align_result(corr, rec, tr, prm, n_obj, iters)
+        out["t_world_obj"], out["correction"], out["max_gap"] = t_out, corr, gap
+        if per_ray:
+            out["obj"], out["dist"], out["t"], out["status_ray"] = obj, dist, th, st
+        return out
+
+    def align_objects_stats(self):
+        """Counts of the last align_objects_to_rays on this engine (dsp_map_align_objects_last_stats): the cast's, summed over its
+        evaluations, the one behind the per-ray outputs included."""
+        c = np.zeros(7, np.int64)
+        L.check(L.load().dsp_map_align_objects_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_align_objects_last_stats")
+        return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5]),
+                "evaluations": int(c[6])}
+
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
         c = np.zeros(5, np.int64)

@@ -147,6 +147,55 @@ def localise_depth(engine, objects, depth, K, t_world_cam0, weights=None, trace=
     return res
 
 
+def refine_poses(engine, objects, pts_world, origins_world, weights=None, only=None, trace=False, **params):
+    """Engine.align_objects_to_rays on the list read_map_objects returns: the sensor poses are known, the OBJECTS are moved to where the
+    world-frame depth rays (measured end points and ray origins, the rays of several frames concatenated) say they are.  only: None (every
+    object) or the ids to refine; the others keep their pose and still occlude.  -> (result, objects): the result dict of
+    Engine.align_objects_to_rays indexed like `objects`, with the per-ray outputs at the returned map and `id` (the map's object id per
+    ray, -1 where the ray is unmatched), and a new object list with the returned poses.  params: max_gap, raycast={...} and the fields of
+    Engine.align_params."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    refine = None
+    if only is not None:
+        ids = [int(o["id"]) for o in objects]
+        missing = [int(i) for i in only if int(i) not in ids]
+        if missing:
+            raise ValueError("refine_poses: no object with id %s in the map" % missing)
+        refine = np.array([i in {int(x) for x in only} for i in ids], np.uint8)
+    res = engine.align_objects_to_rays(poses, [o["code"] for o in objects], pts_world, origins_world, weights=weights, refine=refine, trace=trace,
+                                       per_ray=True, **params)
+    moved = [dict(o, pose=np.asarray(t, np.float64).copy()) for o, t in zip(objects, res["t_world_obj"])]
+    return with_ids(res, [o["id"] for o in objects]), moved
+
+
+def refine_poses_depth(engine, objects, depth, K, t_world_cam, weights=None, only=None, trace=False, **params):
+    """refine_poses on z-depth images of pinhole cameras at KNOWN poses: one image (height, width) with its (4, 4) camera-to-world pose, or
+    lists of both.  Every pixel with a finite positive depth is one ray from its camera's centre (backproject_depth: the convention of
+    pixel_rays and render).  weights: None, or an image per frame.  The result of refine_poses plus `pixel` (the flat row-major pixel index
+    of every ray) and `frame` (the index of its image)."""
+    def images(x):
+        return list(x) if isinstance(x, (list, tuple)) or np.asarray(x).ndim == 3 else [x]
+    frames, cams = images(depth), images(t_world_cam)
+    wimgs = [None] * len(frames) if weights is None else images(weights)
+    if len(cams) != len(frames) or len(wimgs) != len(frames):
+        raise ValueError("refine_poses_depth: one pose (and one weight image) per depth image")
+    pts, org, w, pixel, frame = [], [], [], [], []
+    for f, (img, cam, wimg) in enumerate(zip(frames, cams, wimgs)):
+        p_cam, keep = backproject_depth(img, K)
+        T = np.asarray(cam, np.float64).reshape(4, 4)
+        pts.append((p_cam.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32))
+        org.append(np.broadcast_to(T[:3, 3].astype(np.float32), p_cam.shape).copy())
+        pixel.append(keep)
+        frame.append(np.full(keep.size, f, np.int64))
+        if wimg is not None:
+            w.append(np.asarray(wimg, np.float32).reshape(-1)[keep])
+    res, moved = refine_poses(engine, objects, np.concatenate(pts), np.concatenate(org), weights=np.concatenate(w) if w else None, only=only, trace=trace,
+                              **params)
+    res["pixel"], res["frame"] = np.concatenate(pixel), np.concatenate(frame)
+    return res, moved
+
+
 def with_ids(result, ids):
     """result (an Engine.query_map dict) with `id` added: ids[obj] per point, -1 where obj is -1."""
     out = dict(result)

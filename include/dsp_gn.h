@@ -512,6 +512,55 @@ int dsp_debug_align_ray_rows(int64_t n, const float* origins_world, const float*
 int dsp_debug_align_rays_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const double* t_world_sensor0,
                                int64_t n_hyp, const float* weights, int64_t n_rays, int64_t n_obj);
 
+/* ---- object refinement: where are the OBJECTS, given depth rays from known sensor poses?  One SE(3) correction per map object ----------
+ * The calls above treat the map as fixed and solve for the sensor.  dsp_map_align_objects takes the sensor as known (tracking, bundle
+ * adjustment) and moves the objects to where the depth says they are.  Observation i is the measured end point pts_world[i] of the ray
+ * that runs from origins_world[i] through it, both in the WORLD frame: the caller applies the known sensor poses (map_objects.pixel_rays'
+ * convention), origins are required, and the rays of several frames or sensors are simply concatenated.  weights NULL = ones, finite and
+ * >= 0.  refine: NULL = all ones, or n_obj bytes; an object with 0 is never moved and never evaluated -- it still occludes.
+ * State: one fp64 rigid correction C_k per object, identity at the start; object k stands at T_k = C_k T_k0 (composed in fp64 from the fp32
+ * input, every entry rounded ONCE to fp32; csrc/align_objects_math.h).  One evaluation: the object table comes from the composed poses
+ * through dsp_map_query's inversion; ALL rays go through ONE cast of the map, evaluated objects at their trial pose, every other object at
+ * its accepted pose; gradient, residual, the max_gap gate and the match are dsp_map_align_rays' verbatim.  Ray i belongs to the object
+ * the cast names as its winner, matched or not (an unmatched ray costs that object w rho(max_dist)); a ray without a winner belongs to no
+ * object.  The sums of object k run over its winners in ascending ray order through dsp_map_align's written tree over the LIST (the same
+ * bits whatever the passes, chunks or grid; no float atomics).  The object moves and the measured point stays, C <- exp(xi) C, so the
+ * jacobian is -[g_w, p_w x g_w]: H is dsp_map_align's, b its negation.  Loop, statuses, min_points, damping, step control, tolerances and
+ * step are dsp_map_align's with "hypothesis" = object and pose = C_k.  Objects are coupled only through occlusion; each decides on its own
+ * cost F_k = sum cost / sum w over that evaluation's winners.  LIMIT: the winner set changes between evaluations, so F_k compares means
+ * over different sets of rays.  No ray is ever charged to an object that it does not see.  A composed pose that the map's inversion
+ * refuses ends its object with DSP_ALIGN_SINGULAR at its accepted state.  The jacobian rows of winners of objects that are not evaluated
+ * are decoded and ignored (the winners' chunk plan is the cast's).
+ * Outputs: t_world_obj_out n_obj x 16 floats, the composed poses at the returned states (an object whose correction is still the identity
+ * -- not refined, without support, or never stepped -- returns its input bytes); correction n_obj x 16 doubles; record n_obj x
+ * DSP_ALIGN_RECORD as dsp_map_align's, H being the information of the left perturbation of C_k (an object that is not refined: status
+ * DSP_ALIGN_OK, 0 evaluations); per ray, optional, all four or none (n_rays each): obj, dist, t_hit, status as dsp_map_align_rays reports
+ * them, from ONE extra evaluation of the returned map with every object at its returned pose (run only when asked for, and counted in
+ * the stats); trace optional, n_obj x iterations x DSP_ALIGN_TRACE, the pose traced being C_k.  n_obj and n_rays may be 0: no device is
+ * touched and every refined object returns DSP_ALIGN_NO_SUPPORT with its input pose.  DSP_E_ARG, before the device is touched: a map
+ * dsp_map_query refuses; params dsp_map_align refuses; a raycast dsp_map_raycast refuses; max_gap < max_dist or NaN; NULL origins with
+ * n_rays > 0; a negative or non-finite weight; n_rays > 2^31 - 1; n_obj x ceil(n_rays / 64) pair counts or the objects' code biases beyond
+ * dsp_map_raycast's budgets.
+ * Out of scope: scale or code refinement; a world-axis mask on the degrees of freedom (yaw only); a prior on the correction; the conversion
+ * of H into an edge of dsp_pg_edge_information. */
+int dsp_map_align_objects(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, const float* origins_world,
+                          const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params* params,
+                          const dsp_raycast_params* raycast, double max_gap, float* t_world_obj_out, double* correction, double* record, int32_t* obj,
+                          float* dist, float* t_hit, int32_t* status, double* trace);
+/* Counts of the last dsp_map_align_objects on this handle, laid out as dsp_map_align_rays_last_stats'; the evaluation behind the per-ray
+ * outputs is included. */
+int dsp_map_align_objects_last_stats(dsp_handle* h, int64_t* counts7);
+/* Host only, no handle: csrc/align_objects_math.h on arrays.  dsp_debug_align_objects_rows: n rays' p_w (n x 3), the cast's winner, the
+ * matched object (-1: unmatched), d, g_w (n x 3, read where matched) and w (NULL = ones) -> sums, n_obj x 30 as dsp_debug_align_rows',
+ * per object over its winners through the written tree, b already negated.  dsp_debug_align_objects_compose: n corrections (16 doubles)
+ * and n fp32 poses -> the composed fp32 poses.  dsp_debug_align_objects_check: DSP_E_ARG for what dsp_map_align_objects refuses before it
+ * touches the device, the map's poses and codes excepted; origins_world is only tested against NULL. */
+int dsp_debug_align_objects_rows(int64_t n, const float* pts_world, const int32_t* winner, const int32_t* obj_row, const float* d, const float* grad_world,
+                                 const float* weights, int64_t n_obj, double huber, double max_dist, double* sums);
+int dsp_debug_align_objects_compose(int64_t n, const double* correction, const float* t_world_obj, float* t_world_obj_out);
+int dsp_debug_align_objects_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const float* origins_world,
+                                  const float* weights, int64_t n_rays, int64_t n_obj);
+
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
                      const float* pts, const int64_t* ray_off, const float* rays, const int64_t* depth_off,

@@ -26,6 +26,8 @@ RAYCAST_NORMALS = 1                                                  # dsp_map_r
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_UNDECIDED = 0, 1, 2               # ... a ray's status
 ALIGN_OK, ALIGN_CONVERGED, ALIGN_NO_SUPPORT, ALIGN_SINGULAR = 0, 1, 2, 3      # dsp_map_align: a hypothesis' status
 ALIGN_RECORD, ALIGN_TRACE = 50, 53                                   # ... doubles per record / per traced evaluation
+SHAPES_CODE, SHAPES_POSE, SHAPES_DIM = 1, 2, 70                      # dsp_map_align_shapes: the unknowns asked for, unknowns per object
+SHAPES_RECORD, SHAPES_TRACE, SHAPES_NSUM = 8 + 70 * 70 + 70, 16 + 64 + 4 + 70, 2558
 PREPASS_SMALL_TILES = 0x100
 COMPUTE_F32, COMPUTE_F16, COMPUTE_BF16 = 0, 1, 2
 POSTERIOR_MEAN, POSTERIOR_SUM = 0, 1                       # dsp_batch_posterior: weights
@@ -53,6 +55,10 @@ class AlignParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("min_points", C.c_int32), ("max_dist", C.c_double), ("huber", C.c_double), ("damp", C.c_double),
                 ("trans_tol", C.c_double), ("rot_tol", C.c_double),
                 ("lambda0", C.c_double), ("up", C.c_double), ("down", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
+class ShapesParams(C.Structure):
+    _fields_ = [("unknowns", C.c_int32), ("code_reg", C.c_double), ("code_anchor", C.c_double), ("code_tol", C.c_double)]
 
 
 class RaycastParams(C.Structure):
@@ -203,6 +209,17 @@ SYMBOLS = [
     ("dsp_debug_align_objects_rows", C.c_int, [C.c_int64, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_double, C.c_double, c_f64p]),
     ("dsp_debug_align_objects_compose", C.c_int, [C.c_int64, c_f64p, c_f32p, c_f32p]),
     ("dsp_debug_align_objects_check", C.c_int, [C.POINTER(AlignParams), C.POINTER(RaycastParams), C.c_double, c_f32p, c_f32p, C.c_int64, C.c_int64]),
+    ("dsp_shapes_params_default", None, [C.POINTER(AlignParams), C.POINTER(ShapesParams)]),
+    ("dsp_map_align_shapes", C.c_int, [_VP, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(AlignParams),
+                                       C.POINTER(ShapesParams), C.POINTER(RaycastParams), C.c_double, c_f32p, c_f32p, c_f64p, c_f64p, c_i32p, c_f32p, c_f32p,
+                                       c_i32p, c_f64p]),
+    ("dsp_map_align_shapes_last_stats", C.c_int, [_VP, c_i64p]),
+    ("dsp_debug_align_shapes_rows", C.c_int, [C.c_int64, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_double, C.c_double,
+                                              c_f64p]),
+    ("dsp_debug_align_shapes_step", C.c_int, [c_f64p, c_f64p, C.c_double, c_f64p, c_f32p, C.c_int32, C.POINTER(ShapesParams), C.c_double, C.c_double,
+                                              c_f64p, c_i32p, c_f64p, c_f64p, c_f64p]),
+    ("dsp_debug_align_shapes_check", C.c_int, [C.POINTER(AlignParams), C.POINTER(ShapesParams), C.POINTER(RaycastParams), C.c_double, c_f32p, c_f32p,
+                                               C.c_int64, C.c_int64]),
     ("dsp_debug_split_layout", C.c_int, [C.POINTER(DecoderDesc), c_i32p, c_i32p, c_i64p]),
     ("dsp_debug_mc_table", C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("dsp_debug_code_bias", C.c_int, [C.POINTER(DecoderDesc), c_f32p, c_f32p]),

@@ -21,6 +21,7 @@ SOURCES = [
     "query_kernels.hip",
     "align_kernels.hip",
     "align_objects_kernels.hip",
+    "align_shapes_kernels.hip",
     "raycast_kernels.hip",
     "dsp_gn.hip",
     "decoder_calls.hip",
@@ -59,6 +60,7 @@ def is_stale():
 # contraction off; explicit fmaf() calls stay FMAs.  mlp_kernel.hip keeps the default (its MFMA / fmaf use is explicit anyway).
 EXTRA_FLAGS = {"gn_kernels.hip": ["-ffp-contract=off"], "mesh_kernels.hip": ["-ffp-contract=off"],
                "surface_kernels.hip": ["-ffp-contract=off"], "query_kernels.hip": ["-ffp-contract=off"], "align_kernels.hip": ["-ffp-contract=off"], "align_objects_kernels.hip": ["-ffp-contract=off"],
+               "align_shapes_kernels.hip": ["-ffp-contract=off"],
                "raycast_kernels.hip": ["-ffp-contract=off"],
                "pose_graph.cpp": ["-ffp-contract=off"]}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
@@ -95,7 +97,7 @@ NO_SCRATCH_KERNELS = ("mlp_kernelILi0", "mlp_kernelILi1", "mlp_kernelILi2", "mlp
                       "mlp_lpj_fwd_kernel", "mlp_lpj_bwd_kernel", "k_query_", "k_align_", "k_raycast_")
 DECODER_SOURCES = ("mlp_kernel.hip", "mlp_lp_kernel.hip", "mlp_lpj_kernel.hip", "mlp_split_kernel.hip", "mlp_cluster_kernel.hip")
 # bandwidth-bound kernels that are only held to "no scratch": their register and scratch figures join the report, the M0 / LDS-DMA rules do not apply
-PLAIN_SOURCES = ("query_kernels.hip", "align_kernels.hip", "align_objects_kernels.hip", "raycast_kernels.hip")
+PLAIN_SOURCES = ("query_kernels.hip", "align_kernels.hip", "align_objects_kernels.hip", "align_shapes_kernels.hip", "raycast_kernels.hip")
 
 
 class IsaCheckError(RuntimeError):

@@ -35,8 +35,8 @@
 // Jacobian rows of objects that are not evaluated (not refined, or ended) are still decoded by the cast's winner pass and ignored: the
 // chunk plan is shared with dsp_map_raycast and cutting objects out of it would change it.
 //
-// Out of scope: scale or code refinement; a world-axis mask on the six degrees of freedom (yaw only); a prior on the correction; the
-// conversion of H into an edge of dsp_pg_edge_information.
+// Code refinement is dsp_map_align_shapes (align_shapes_math.h).  Out of scope: scale; a world-axis mask on the six degrees of freedom (yaw
+// only); a prior on the correction; the conversion of H into an edge of dsp_pg_edge_information.
 #pragma once
 #include "align_math.h"
 #include "align_rays_math.h"

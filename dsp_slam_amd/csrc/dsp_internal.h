@@ -656,4 +656,22 @@ void align_objects_directions_host(int64_t n, const float* org_w, const float* p
 void align_objects_rows_host(int64_t n, const float* pts_w, const int32_t* winner, const int32_t* obj_row, const float* d_row, const float* grad_w,
                              const float* weights, int64_t n_obj, double huber, double max_dist, double* sums);
 
+// ---- shape refinement (align_shapes_kernels.hip; the arithmetic: align_shapes_math.h) ------------
+// rows: behind a chunk of the winners' jacobian rows (next to launch_align_rays_gradient), gcode[ray][64] <- the row's code derivatives times
+// the winner's scale.  gram: the lists and the block table of launch_align_objects_list / _gram with blocks of align_shapes_math::BLOCK
+// positions -> slab[q][align_shapes_math::NSUM], then sums[k][NSUM] <- the slabs [first[k], first[k + 1]) in ascending order.
+hipError_t launch_align_shapes_rows(const float* rows, const int2* row_meta, int n_rows, const float* tab, int n_obj, int64_t n_rays, float* gcode,
+                                    hipStream_t s);
+hipError_t launch_align_shapes_gram(const int4* blocks, int n_blocks, const int* first, int n_obj, const int* win_ray, int n_list, int n_rays,
+                                    const float* pts_w, const int* obj_row, const float* d_row, const float* grad_w, const float* gcode,
+                                    const float* weights, double huber, double max_dist, double* slab, double* sums, hipStream_t s);
+// align_shapes_math.h compiled for the host in the translation unit that has contraction off (dsp_map_align_shapes, dsp_debug_align_shapes_*)
+void align_shapes_rows_host(int64_t n, const float* pts_w, const int32_t* winner, const int32_t* obj_row, const float* d_row, const float* grad_w,
+                            const float* gcode, const float* weights, int64_t n_obj, double huber, double max_dist, double* sums);
+double align_shapes_mean_cost_host(const double* sums, double huber, double max_dist);
+double align_shapes_cost_host(double mean, const double* z, const double* z0, int code_len, double code_reg, double code_anchor);
+bool align_shapes_solve_host(const double* H, const double* b, double W, const double* z, const double* z0, int code_len, int unknowns, double code_reg,
+                             double code_anchor, double damp, double lambda, double* dx);
+void align_shapes_apply_step_host(const double* dx, int unknowns, int code_len, const double* c_in, const double* z_in, double* c_out, double* z_out);
+
 }  // namespace dsp

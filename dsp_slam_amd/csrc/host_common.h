@@ -264,6 +264,7 @@ struct dsp_handle {
     int64_t r_stats[6] = {0, 0, 0, 0, 0, 0};    // pairs, decoder rows, tiles, rounds run, passes, exhausted pairs
     int64_t ar_stats[7] = {0, 0, 0, 0, 0, 0, 0};    // ray alignment (align_rays_run): the six above summed over the evaluations, evaluations
     int64_t ao_stats[7] = {0, 0, 0, 0, 0, 0, 0};    // object refinement (align_objects_run): likewise, the extra evaluation behind the per-ray outputs included
+    int64_t as_stats[7] = {0, 0, 0, 0, 0, 0, 0};    // shape refinement (align_shapes_run): likewise
     // dsp_mesh_last_stats: prepass points, fp32 band points, fp32 audit points, points decoded densely in fp32, objects re-run dense;
     // largest guard error
     int64_t ms_counts[5] = {0, 0, 0, 0, 0};

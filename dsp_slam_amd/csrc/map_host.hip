@@ -1,11 +1,13 @@
 // The object map on the host: signed distance and normal of world points (dsp_map_query) and the alignment of a point cloud to the map
 // (dsp_map_align), which runs the query's core; ray casting (dsp_map_raycast) and the alignment of depth rays to the map
 // (dsp_map_align_rays), which runs the cast's core inside the alignment's hypothesis loop; the refinement of the objects' own poses against
-// world-frame depth rays (dsp_map_align_objects), which runs the same loop with one correction per object; with their C ABI.
+// world-frame depth rays (dsp_map_align_objects), which runs the same loop with one correction per object; the refinement of the objects'
+// shape codes against the same rays (dsp_map_align_shapes), a sibling loop whose state carries a code; with their C ABI.
 #include "decoder_calls.h"
 #include "decoder_pack.h"
 #include "query_math.h"     // constants only: the arithmetic is compiled in query_kernels.hip (contraction off)
 #include "align_math.h"     // constants only, likewise (align_kernels.hip; the ray alignment's arithmetic, align_rays_math.h, is compiled there too)
+#include "align_shapes_math.h"      // constants only, likewise (align_shapes_kernels.hip)
 
 #include <algorithm>
 #include <cmath>
@@ -991,6 +993,259 @@ void align_objects_run(dsp_handle* h, const std::vector<float>& tab0, const floa
     write_out();
 }
 
+// ------------------------------------------------------------------------------------------------
+// shape refinement (dsp_map_align_shapes; arithmetic: align_shapes_math.h, kernels: align_shapes_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+const char* align_shapes_check_params(const dsp_shapes_params& sp) {
+    if (sp.unknowns == 0 || (sp.unknowns & ~(DSP_SHAPES_CODE | DSP_SHAPES_POSE))) return "align_shapes: unknowns must be DSP_SHAPES_CODE, DSP_SHAPES_POSE or both";
+    if (!std::isfinite(sp.code_reg) || sp.code_reg < 0.0 || !std::isfinite(sp.code_anchor) || sp.code_anchor < 0.0)
+        return "align_shapes: code_reg and code_anchor must be finite and >= 0";
+    if (!std::isfinite(sp.code_tol) || sp.code_tol < 0.0) return "align_shapes: code_tol must be finite and >= 0";
+    return nullptr;
+}
+
+// one object on the host: the accepted state (C, z) with its sums, and the state to evaluate next
+struct ShapeHyp {
+    double C_acc[16], C_eval[16], z_acc[CODE_LEN], z_eval[CODE_LEN], z0[CODE_LEN];
+    std::vector<double> S;              // the sums at the accepted state
+    double F_acc = 0.0, F0 = 0.0, lam = 0.0;
+    bool live = true, has_acc = false;
+    int status = DSP_ALIGN_OK, evals = 0, steps = 0;
+};
+
+// The sibling of align_objects_run whose state carries a code: the same uploads, cast, lists and block table (blocks of
+// align_shapes_math::BLOCK positions); per evaluation the host also sends the code biases of the objects' evaluated codes and reads
+// align_shapes_math::NSUM doubles per object.  The loop is align_loop's with the 70-dimensional step.
+void align_shapes_run(dsp_handle* h, const std::vector<float>& tab0, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts,
+                      const float* origins, const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params& prm,
+                      const dsp_shapes_params& sprm, const raycast_math::Params& rprm, double max_gap, float* t_out, float* codes_out, double* correction,
+                      double* record, int32_t* obj, float* dist, float* t_hit, int32_t* status, double* trace) {
+    namespace sm = align_shapes_math;
+    constexpr int NS = sm::NSUM, DIM = sm::DIM;
+    const int iters = prm.iterations, code_len = h->code_len, unknowns = sprm.unknowns;
+    for (auto& c : h->as_stats) c = 0;
+    if (trace) std::fill(trace, trace + (size_t)n_obj * iters * DSP_SHAPES_TRACE, 0.0);
+    auto no_rays = [&] {
+        if (obj)
+            for (int64_t r = 0; r < n_rays; ++r) { obj[r] = -1; dist[r] = t_hit[r] = INFINITY; status[r] = raycast_math::STATUS_MISS; }
+    };
+    if (n_obj == 0) { no_rays(); return; }
+    const std::vector<double> zero((size_t)NS, 0.0);
+    std::vector<ShapeHyp> hyp((size_t)n_obj);
+    for (int64_t k = 0; k < n_obj; ++k) {
+        ShapeHyp& a = hyp[k];
+        for (int i = 0; i < 16; ++i) a.C_acc[i] = a.C_eval[i] = (i % 5 == 0) ? 1.0 : 0.0;
+        for (int c = 0; c < CODE_LEN; ++c) a.z0[c] = a.z_acc[c] = a.z_eval[c] = (double)codes[k * CODE_LEN + c];
+        a.S = zero;
+        a.F0 = a.F_acc = align_shapes_cost_host(align_shapes_mean_cost_host(zero.data(), prm.huber, prm.max_dist), a.z0, a.z0, code_len, sprm.code_reg,
+                                                sprm.code_anchor);
+        if (refine && !refine[k]) a.live = false;                       // never evaluated: status OK, 0 evaluations
+        else if (n_rays == 0) { a.live = false; a.status = DSP_ALIGN_NO_SUPPORT; }
+    }
+    // the fp32 code an object is decoded with: the input's own bytes as long as the fp64 code is the input's
+    auto code32 = [&](int64_t k, const double* z, float* out) {
+        for (int c = 0; c < CODE_LEN; ++c)
+            out[c] = (z[c] == hyp[k].z0[c] || memcmp(z + c, hyp[k].z0 + c, sizeof(double)) == 0) ? codes[k * CODE_LEN + c] : (float)z[c];
+        if (!(unknowns & DSP_SHAPES_CODE)) memcpy(out, codes + k * CODE_LEN, CODE_LEN * sizeof(float));
+    };
+    auto write_out = [&] {
+        for (int64_t k = 0; k < n_obj; ++k) {
+            const ShapeHyp& a = hyp[k];
+            memcpy(correction + 16 * k, a.C_acc, sizeof a.C_acc);
+            align_objects_compose_host(a.C_acc, t_world_obj + 16 * k, t_out + 16 * k);
+            code32(k, a.z_acc, codes_out + k * CODE_LEN);
+            double* rec = record + (size_t)DSP_SHAPES_RECORD * k;
+            rec[0] = a.status; rec[1] = a.evals; rec[2] = a.steps; rec[3] = a.F0; rec[4] = a.F_acc;
+            rec[5] = a.S[sm::IDX_N]; rec[6] = a.S[sm::IDX_W]; rec[7] = a.lam;
+            int q = sm::IDX_H;
+            for (int i = 0; i < DIM; ++i)
+                for (int j = i; j < DIM; ++j) rec[8 + DIM * i + j] = rec[8 + DIM * j + i] = a.S[q++];
+            for (int i = 0; i < DIM; ++i) rec[8 + DIM * DIM + i] = a.S[sm::IDX_B + i];
+        }
+    };
+    bool any = false;
+    for (const ShapeHyp& a : hyp) any = any || a.live;
+    if (n_rays == 0 || (!any && !obj)) { no_rays(); write_out(); return; }
+    HIP_TRY(hipSetDevice(h->device));
+    DevBuf<float> a_pts, a_org, a_dir, a_w, a_grad, a_gcode, c_tab, c_cb, m_dist;
+    DevBuf<int> m_obj, a_off, a_first, a_win;
+    DevBuf<int4> a_blocks;
+    DevBuf<double> a_slab, a_sums;
+    RaycastWork w;
+    std::vector<float> cb((size_t)n_obj * 2 * WIDTH), dirs((size_t)n_rays * 3), tab((size_t)n_obj * query_math::OBJ_STRIDE, 0.f);
+    std::vector<int> off((size_t)n_obj), first((size_t)n_obj + 1);
+    std::vector<int4> blocks;
+    std::vector<double> sums((size_t)n_obj * NS, 0.0);
+    SyncOnExit sync_on_exit{h->stream};
+    QueryTimer timer{h->q_timing, h->stream, {}};
+    h->q_ms[0] = h->q_ms[1] = 0.0;
+    timer.mark();
+    align_objects_directions_host(n_rays, origins, pts, dirs.data());
+    a_pts.alloc((size_t)n_rays * 3);
+    a_org.alloc((size_t)n_rays * 3);
+    a_dir.alloc((size_t)n_rays * 3);
+    if (weights) a_w.alloc((size_t)n_rays);
+    a_grad.alloc((size_t)n_rays * 3);
+    a_gcode.alloc((size_t)n_rays * CODE_LEN);
+    c_tab.alloc(tab.size());
+    c_cb.alloc(cb.size());
+    m_obj.alloc((size_t)n_rays);
+    m_dist.alloc((size_t)n_rays);
+    a_off.alloc((size_t)n_obj);
+    a_first.alloc((size_t)n_obj + 1);
+    a_win.alloc((size_t)n_rays);
+    a_sums.alloc((size_t)n_obj * NS);
+    HIP_TRY(hipMemcpyAsync(a_pts.p, pts, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_org.p, origins, (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_dir.p, dirs.data(), (size_t)n_rays * 12, hipMemcpyHostToDevice, h->stream));
+    if (weights) HIP_TRY(hipMemcpyAsync(a_w.p, weights, (size_t)n_rays * 4, hipMemcpyHostToDevice, h->stream));
+    const RaycastRows gradient = [&](const RaycastDev&, const float* rows, const int2* row_meta, int n) {
+        HIP_TRY(launch_align_rays_gradient(rows, row_meta, n, c_tab.p, (int)n_obj, n_rays, a_grad.p, h->stream));
+        HIP_TRY(launch_align_shapes_rows(rows, row_meta, n, c_tab.p, (int)n_obj, n_rays, a_gcode.p, h->stream));
+    };
+    // The object table and the code biases at the trial states of the evaluated objects (trial) or at every object's accepted state.  A trial
+    // code or bias that is not finite, or a trial pose the map's inversion refuses, ends its object with SINGULAR at its accepted state.
+    auto table = [&](bool trial) {
+        for (int64_t k = 0; k < n_obj; ++k) {
+            ShapeHyp& a = hyp[k];
+            float pose[16], z32[CODE_LEN];
+            float* e = tab.data() + k * query_math::OBJ_STRIDE;
+            float* bias = cb.data() + (size_t)k * 2 * WIDTH;
+            bool ok = false;
+            if (trial && a.live) {
+                align_objects_compose_host(a.C_eval, t_world_obj + 16 * k, pose);
+                ok = query_invert_host(pose, e, e + 12);
+                code32(k, a.z_eval, z32);
+                code_bias_host(h->h_codew, h->h_b0, h->h_blat, z32, bias);
+                if (ok && a.has_acc) {          // the first evaluation is the input's: the map's own rule for a code that is not finite holds
+                    for (int c = 0; c < CODE_LEN; ++c) ok = ok && std::isfinite(z32[c]);
+                    for (int c = 0; c < 2 * WIDTH; ++c) ok = ok && std::isfinite(bias[c]);
+                }
+                if (!ok) { a.live = false; a.status = DSP_ALIGN_SINGULAR; }
+            }
+            if (!ok) {
+                align_objects_compose_host(a.C_acc, t_world_obj + 16 * k, pose);
+                if (!query_invert_host(pose, e, e + 12)) throw std::runtime_error("align_shapes: an accepted pose is not invertible");
+                code32(k, a.z_acc, z32);
+                code_bias_host(h->h_codew, h->h_b0, h->h_blat, z32, bias);
+            }
+            e[13] = std::isnan(tab0[(size_t)k * query_math::OBJ_STRIDE + 13]) ? std::nanf("") : e[12];     // a code that is not finite never wins
+        }
+    };
+    // table and biases up, the cast with the winners' gradients behind it, the rows' (obj, d): the stream is NOT synchronised behind it
+    auto cast = [&](bool trial) {
+        table(trial);
+        HIP_TRY(hipMemcpyAsync(c_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(c_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, h->stream));
+        raycast_core(h, w, a_org.p, a_dir.p, c_tab.p, c_cb.p, n_obj, n_rays, rprm, nullptr, timer, h->as_stats, gradient);
+        HIP_TRY(launch_align_rays_residual(a_org.p, a_dir.p, w.r_obj.p, w.r_t.p, w.r_dist.p, w.r_status.p, a_grad.p, n_rays, max_gap, m_obj.p, m_dist.p,
+                                           h->stream));
+    };
+    auto evaluate = [&] {
+        cast(true);
+        // w.cnt: the winners per object, read back by the cast.  The lists of ALL objects, blocks for the evaluated ones
+        int64_t n_list = 0;
+        blocks.clear();
+        for (int64_t k = 0; k < n_obj; ++k) {
+            off[k] = (int)n_list;
+            first[k] = (int)blocks.size();
+            if (hyp[k].live)
+                for (int j = 0; j < w.cnt[k]; j += sm::BLOCK) blocks.push_back(make_int4((int)k, (int)n_list + j, std::min(sm::BLOCK, w.cnt[k] - j), 0));
+            n_list += w.cnt[k];
+        }
+        first[n_obj] = (int)blocks.size();
+        if (n_list > n_rays) throw std::runtime_error("align_shapes: more winners than rays");
+        a_blocks.ensure(blocks.size());
+        a_slab.ensure(blocks.size() * NS);
+        HIP_TRY(hipMemcpyAsync(a_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(a_first.p, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (!blocks.empty()) HIP_TRY(hipMemcpyAsync(a_blocks.p, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(launch_align_objects_list(w.r_obj.p, (int)n_rays, (int)n_obj, (int)((n_rays + 63) / 64), w.r_wave_cnt.p, a_off.p, (int)n_list, a_win.p,
+                                          h->stream));
+        HIP_TRY(launch_align_shapes_gram(a_blocks.p, (int)blocks.size(), a_first.p, (int)n_obj, a_win.p, (int)n_list, (int)n_rays, a_pts.p, m_obj.p, m_dist.p,
+                                         a_grad.p, a_gcode.p, weights ? a_w.p : nullptr, prm.huber, prm.max_dist, a_slab.p, a_sums.p, h->stream));
+        HIP_TRY(hipMemcpyAsync(sums.data(), a_sums.p, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));    // the sums; w's uploads, the table, the biases and the block table have been consumed
+        raycast_core_stats(w, h->as_stats);
+    };
+    const step_rule::Params sp{prm.lambda0, prm.up, prm.down, prm.lambda_min, prm.lambda_max};
+    const bool step_on = !step_rule::is_off(sp);
+    auto end = [](ShapeHyp& a, int st) { a.live = false; a.status = st; };
+    std::vector<double> H((size_t)DIM * DIM);
+    for (int e = 0; e < iters; ++e) {
+        any = false;
+        for (const ShapeHyp& a : hyp) any = any || a.live;
+        if (!any) break;
+        evaluate();
+        h->as_stats[6] += 1;
+        for (int64_t k = 0; k < n_obj; ++k) {
+            ShapeHyp& a = hyp[k];
+            if (!a.live) continue;          // also an object whose trial state the table refused
+            const double* S = sums.data() + k * NS;
+            const double F = align_shapes_cost_host(align_shapes_mean_cost_host(S, prm.huber, prm.max_dist), a.z_eval, a.z0, code_len, sprm.code_reg,
+                                                    sprm.code_anchor);
+            const bool support = S[sm::IDX_N] >= (double)prm.min_points;
+            double* tr = trace ? trace + ((size_t)k * iters + e) * DSP_SHAPES_TRACE : nullptr;
+            a.evals += 1;
+            if (e == 0) a.F0 = F;
+            int dec = step_rule::ACCEPTED;
+            if (step_on)
+                dec = !a.has_acc ? step_rule::decide(true, F, 0.0, sp, a.lam)
+                                 : step_rule::decide(false, support ? F : (double)INFINITY, a.F_acc, sp, a.lam);
+            if (dec == step_rule::ACCEPTED) {
+                if (a.has_acc) a.steps += 1;
+                memcpy(a.C_acc, a.C_eval, sizeof a.C_acc);
+                memcpy(a.z_acc, a.z_eval, sizeof a.z_acc);
+                a.S.assign(S, S + NS);
+                a.F_acc = F;
+                a.has_acc = true;
+            }
+            if (tr) {
+                memcpy(tr, a.C_eval, sizeof a.C_eval);
+                memcpy(tr + 16, a.z_eval, sizeof a.z_eval);
+                tr[80] = dec; tr[81] = F; tr[82] = a.lam; tr[83] = S[sm::IDX_N];
+            }
+            // the step from the accepted state
+            if (a.S[sm::IDX_N] < (double)prm.min_points) { end(a, DSP_ALIGN_NO_SUPPORT); continue; }
+            double dx[DIM];
+            int q = sm::IDX_H;
+            for (int i = 0; i < DIM; ++i)
+                for (int j = i; j < DIM; ++j) H[(size_t)DIM * i + j] = H[(size_t)DIM * j + i] = a.S[q++];
+            bool solved = false;
+            for (int tries = 0; !solved; ++tries) {
+                solved = align_shapes_solve_host(H.data(), a.S.data() + sm::IDX_B, a.S[sm::IDX_W], a.z_acc, a.z0, code_len, unknowns, sprm.code_reg,
+                                                 sprm.code_anchor, prm.damp, a.lam, dx);
+                if (solved || !step_on || tries >= 64 || !(a.lam < sp.lambda_max)) break;
+                a.lam = fmin(fmax(a.lam, sp.lambda_min) * sp.up, sp.lambda_max);        // a failed factorisation: lambda grows like after a rejection
+            }
+            if (tr) tr[82] = a.lam;
+            if (!solved) { end(a, DSP_ALIGN_SINGULAR); continue; }
+            if (tr) memcpy(tr + 84, dx, sizeof dx);
+            double mv = 0.0, mw = 0.0, mz = 0.0;
+            for (int i = 0; i < 3; ++i) { mv = fmax(mv, fabs(dx[i])); mw = fmax(mw, fabs(dx[3 + i])); }
+            for (int c = 0; c < CODE_LEN; ++c) mz = fmax(mz, fabs(dx[6 + c]));
+            if (mv < prm.trans_tol && mw < prm.rot_tol && mz < sprm.code_tol) { end(a, DSP_ALIGN_CONVERGED); continue; }
+            if (e == iters - 1) { end(a, DSP_ALIGN_OK); continue; }
+            align_shapes_apply_step_host(dx, unknowns, code_len, a.C_acc, a.z_acc, a.C_eval, a.z_eval);
+        }
+    }
+    if (obj) {      // one more evaluation of the returned map, every object at its returned state
+        cast(false);
+        h->as_stats[6] += 1;
+        HIP_TRY(hipMemcpyAsync(obj, m_obj.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(dist, m_dist.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(t_hit, w.r_t.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(status, w.r_status.p, (size_t)n_rays * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    timer.mark();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    timer.read(h->q_ms);
+    if (obj) raycast_core_stats(w, h->as_stats);
+    write_out();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1166,6 +1421,74 @@ int dsp_debug_align_objects_rows(int64_t n, const float* pts_world, const int32_
 int dsp_debug_align_objects_compose(int64_t n, const double* correction, const float* t_world_obj, float* t_world_obj_out) {
     if (n < 0 || (n > 0 && (!correction || !t_world_obj || !t_world_obj_out))) return DSP_E_ARG;
     for (int64_t k = 0; k < n; ++k) align_objects_compose_host(correction + 16 * k, t_world_obj + 16 * k, t_world_obj_out + 16 * k);
+    return DSP_OK;
+}
+
+void dsp_shapes_params_default(dsp_align_params* params, dsp_shapes_params* shapes) {
+    if (params) {
+        dsp_align_params_default(params);
+        params->damp = 1e-4;
+    }
+    if (shapes) *shapes = dsp_shapes_params{DSP_SHAPES_CODE, 0.0, 0.0, 1e-6};
+}
+
+int dsp_map_align_shapes(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, const float* origins_world,
+                         const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params* params,
+                         const dsp_shapes_params* shapes, const dsp_raycast_params* raycast, double max_gap, float* t_world_obj_out, float* codes_out,
+                         double* correction, double* record, int32_t* obj, float* dist, float* t_hit, int32_t* status, double* trace) {
+    if (!h || !params || !shapes || !raycast || n_obj < 0 || n_rays < 0) return DSP_E_ARG;
+    const int n_out = (obj != nullptr) + (dist != nullptr) + (t_hit != nullptr) + (status != nullptr);
+    if (n_out != 0 && n_out != 4) return DSP_E_ARG;
+    if ((n_obj > 0 && (!t_world_obj || !codes || !t_world_obj_out || !codes_out || !correction || !record)) || (n_rays > 0 && !pts_world)) return DSP_E_ARG;
+    return guarded(h, [&] {
+        if (const char* why = align_objects_check_inputs(*params, *raycast, max_gap, origins_world, weights, n_rays, n_obj)) throw std::invalid_argument(why);
+        if (const char* why = align_shapes_check_params(*shapes)) throw std::invalid_argument(why);
+        const std::vector<float> tab = query_table(h, t_world_obj, codes, n_obj);
+        align_shapes_run(h, tab, t_world_obj, codes, n_obj, pts_world, origins_world, weights, n_rays, refine, *params, *shapes, raycast_params(*raycast),
+                         max_gap, t_world_obj_out, codes_out, correction, record, obj, dist, t_hit, status, trace);
+    });
+}
+
+int dsp_map_align_shapes_last_stats(dsp_handle* h, int64_t* counts7) {
+    if (!h || !counts7) return DSP_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    memcpy(counts7, h->as_stats, sizeof h->as_stats);
+    return DSP_OK;
+}
+
+int dsp_debug_align_shapes_check(const dsp_align_params* params, const dsp_shapes_params* shapes, const dsp_raycast_params* raycast, double max_gap,
+                                 const float* origins_world, const float* weights, int64_t n_rays, int64_t n_obj) {
+    if (!params || !shapes || !raycast || n_rays < 0 || n_obj < 0 || n_obj > QUERY_MAX_OBJ) return DSP_E_ARG;
+    if (align_shapes_check_params(*shapes)) return DSP_E_ARG;
+    return align_objects_check_inputs(*params, *raycast, max_gap, origins_world, weights, n_rays, n_obj) ? DSP_E_ARG : DSP_OK;
+}
+
+int dsp_debug_align_shapes_rows(int64_t n, const float* pts_world, const int32_t* winner, const int32_t* obj_row, const float* d, const float* grad_world,
+                                const float* gcode, const float* weights, int64_t n_obj, double huber, double max_dist, double* sums) {
+    if (n < 0 || n_obj < 0 || (n_obj > 0 && !sums) || (n > 0 && (!pts_world || !winner || !obj_row || !d || !grad_world || !gcode))) return DSP_E_ARG;
+    if (!std::isfinite(max_dist) || !std::isfinite(huber) || !(huber > 0.0) || !(huber <= max_dist)) return DSP_E_ARG;
+    try {
+        align_shapes_rows_host(n, pts_world, winner, obj_row, d, grad_world, gcode, weights, n_obj, huber, max_dist, sums);
+    } catch (const std::bad_alloc&) {
+        return DSP_E_NOMEM;
+    }
+    return DSP_OK;
+}
+
+int dsp_debug_align_shapes_step(const double* H4900, const double* b70, double W, const double* code, const float* code0, int32_t code_len,
+                                const dsp_shapes_params* shapes, double damp, double lambda, const double* c16, int32_t* status, double* dx70,
+                                double* c_trial16, double* code_trial64) {
+    if (!H4900 || !b70 || !code || !code0 || !shapes || !c16 || !status || !dx70 || !c_trial16 || !code_trial64) return DSP_E_ARG;
+    if (code_len < 1 || code_len > CODE_LEN || align_shapes_check_params(*shapes)) return DSP_E_ARG;
+    double z0[CODE_LEN], dx[DSP_SHAPES_DIM];
+    for (int c = 0; c < CODE_LEN; ++c) z0[c] = (double)code0[c];
+    if (!align_shapes_solve_host(H4900, b70, W, code, z0, code_len, shapes->unknowns, shapes->code_reg, shapes->code_anchor, damp, lambda, dx)) {
+        *status = DSP_ALIGN_SINGULAR;
+        return DSP_OK;
+    }
+    *status = DSP_ALIGN_OK;
+    memcpy(dx70, dx, sizeof dx);
+    align_shapes_apply_step_host(dx, shapes->unknowns, code_len, c16, code, c_trial16, code_trial64);
     return DSP_OK;
 }
 

@@ -1117,6 +1117,94 @@ class Engine(object):
         return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5]),
                 "evaluations": int(c[6])}
 
+    # -- shape refinement ---------------------------------------------------------------------------
+    UNKNOWNS = {"code": L.SHAPES_CODE, "pose": L.SHAPES_POSE, "pose+code": L.SHAPES_CODE | L.SHAPES_POSE, "code+pose": L.SHAPES_CODE | L.SHAPES_POSE}
+
+    @classmethod
+    def shapes_params(cls, unknowns="code", code_reg=None, code_anchor=None, code_tol=None, **params):
+        """(dsp_align_params, dsp_shapes_params) of align_shapes_to_rays: dsp_shapes_params_default's values (align_params' but damp 1e-4;
+        code only, no regulariser, code_tol 1e-6) with the arguments written over them."""
+        sp = L.ShapesParams()
+        dflt = L.AlignParams()
+        L.load().dsp_shapes_params_default(C.byref(dflt), C.byref(sp))
+        params.setdefault("damp", dflt.damp)
+        prm = cls.align_params(**params)
+        if unknowns not in cls.UNKNOWNS:
+            raise ValueError("unknowns must be 'code', 'pose' or 'pose+code'")
+        sp.unknowns = cls.UNKNOWNS[unknowns]
+        for name, v in (("code_reg", code_reg), ("code_anchor", code_anchor), ("code_tol", code_tol)):
+            if v is not None:
+                setattr(sp, name, float(v))
+        return prm, sp
+
+    def align_shapes_to_rays(self, t_world_obj, codes, pts_world, origins_world, weights=None, refine=None, trace=False, per_ray=False,
+                             max_gap=None, raycast=None, unknowns="code", code_reg=None, code_anchor=None, code_tol=None, **params):
+        """What shape do the objects have, given depth rays from known sensor poses?  One 70-dimensional Gauss-Newton system per map object
+        -- 6 pose and 64 code unknowns -- against the ray-cast map (dsp_map_align_shapes).  Rays, weights, refine, max_gap, raycast and
+        params as align_objects_to_rays (damp defaults to 1e-4, on the mean system); unknowns: "code", "pose" or "pose+code"; code_reg:
+        weight of |z|^2, code_anchor: weight of |z - z_input|^2 (both 0 by default); code_tol: the code's convergence tolerance.  The dict of
+        align_objects_to_rays plus `codes` (n_obj, 64) float32, with `information` (n_obj, 70, 70) and `b` (n_obj, 70) the raw sums of
+        x = [v, omega, dz]; the trace holds pose, code, decision, cost, lambda, n_used and dx (70)."""
+        t = L.f32(np.asarray(t_world_obj, np.float32).reshape(-1, 4, 4))
+        n_obj = t.shape[0]
+        codes = np.stack([L.code64(c) for c in codes]) if len(codes) else np.zeros((0, L.CODE_LEN), np.float32)
+        if codes.shape[0] != n_obj:
+            raise ValueError("one code per pose")
+        pts = L.f32(np.asarray(pts_world, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        org = None
+        if origins_world is not None:
+            org = L.f32(np.asarray(origins_world, np.float32).reshape(-1, 3))
+            if org.shape[0] != n:
+                raise ValueError("one origin per point")
+        w = None
+        if weights is not None:
+            w = L.f32(np.asarray(weights, np.float32).reshape(-1))
+            if w.shape[0] != n:
+                raise ValueError("one weight per ray")
+        ref = None
+        if refine is not None:
+            ref = np.ascontiguousarray(np.asarray(refine).reshape(-1) != 0, np.uint8)
+            if ref.shape[0] != n_obj:
+                raise ValueError("one refine flag per object")
+        prm, sp = self.shapes_params(unknowns, code_reg, code_anchor, code_tol, **params)
+        rprm = self.raycast_params(**(raycast or {}))
+        lib = L.load()
+        gap = float(lib.dsp_align_rays_default_max_gap(C.byref(prm))) if max_gap is None else float(max_gap)
+        iters = max(int(prm.iterations), 0)
+        D = L.SHAPES_DIM
+        t_out, corr = np.zeros((n_obj, 4, 4), np.float32), np.zeros((n_obj, 4, 4), np.float64)
+        c_out = np.zeros((n_obj, L.CODE_LEN), np.float32)
+        rec = np.zeros((n_obj, L.SHAPES_RECORD), np.float64)
+        obj = np.zeros(n, np.int32) if per_ray else None
+        dist = np.zeros(n, np.float32) if per_ray else None
+        th = np.zeros(n, np.float32) if per_ray else None
+        st = np.zeros(n, np.int32) if per_ray else None
+        tr = np.zeros((n_obj, iters, L.SHAPES_TRACE), np.float64) if trace else None
+        L.check(lib.dsp_map_align_shapes(self._h, L.ptr(t), L.ptr(codes), n_obj, L.ptr(pts), L.ptr(org), L.ptr(w), n, L.ptr(ref, C.POINTER(C.c_uint8)),
+                                         C.byref(prm), C.byref(sp), C.byref(rprm), gap, L.ptr(t_out), L.ptr(c_out), L.ptr(corr, L.c_f64p),
+                                         L.ptr(rec, L.c_f64p), L.ptr(obj, L.c_i32p), L.ptr(dist), L.ptr(th), L.ptr(st, L.c_i32p), L.ptr(tr, L.c_f64p)),
+                self._h, "dsp_map_align_shapes")
+        out = {"pose": corr, "status": rec[:, 0].astype(np.int32), "evaluations": rec[:, 1].astype(np.int32), "steps": rec[:, 2].astype(np.int32),
+               "cost0": rec[:, 3].copy(), "cost": rec[:, 4].copy(), "n_used": rec[:, 5].astype(np.int64), "sum_w": rec[:, 6].copy(),
+               "lambda": rec[:, 7].copy(), "information": rec[:, 8:8 + D * D].reshape(n_obj, D, D).copy(), "b": rec[:, 8 + D * D:].copy()}
+        ok = np.flatnonzero(out["n_used"] >= prm.min_points)
+        out["best"] = int(ok[np.argmin(out["cost"][ok])]) if ok.size else -1
+        if tr is not None:
+            out["trace"] = {"pose": tr[:, :, :16].reshape(n_obj, iters, 4, 4).copy(), "code": tr[:, :, 16:80].copy(), "decision": tr[:, :, 80].astype(np.int32),
+                            "cost": tr[:, :, 81].copy(), "lambda": tr[:, :, 82].copy(), "n_used": tr[:, :, 83].astype(np.int64), "dx": tr[:, :, 84:].copy()}
+        out["t_world_obj"], out["correction"], out["codes"], out["max_gap"] = t_out, corr, c_out, gap
+        if per_ray:
+            out["obj"], out["dist"], out["t"], out["status_ray"] = obj, dist, th, st
+        return out
+
+    def align_shapes_stats(self):
+        """Counts of the last align_shapes_to_rays on this engine (dsp_map_align_shapes_last_stats), laid out as align_objects_stats'."""
+        c = np.zeros(7, np.int64)
+        L.check(L.load().dsp_map_align_shapes_last_stats(self._h, L.ptr(c, L.c_i64p)), self._h, "dsp_map_align_shapes_last_stats")
+        return {"pairs": int(c[0]), "rows": int(c[1]), "tiles": int(c[2]), "rounds": int(c[3]), "passes": int(c[4]), "exhausted": int(c[5]),
+                "evaluations": int(c[6])}
+
     def mesh_stats(self):
         """Counts of the last mesh extraction on this engine (dsp_mesh_last_stats)."""
         c = np.zeros(5, np.int64)

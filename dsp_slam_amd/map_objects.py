@@ -169,17 +169,14 @@ def refine_poses(engine, objects, pts_world, origins_world, weights=None, only=N
     return with_ids(res, [o["id"] for o in objects]), moved
 
 
-def refine_poses_depth(engine, objects, depth, K, t_world_cam, weights=None, only=None, trace=False, **params):
-    """refine_poses on z-depth images of pinhole cameras at KNOWN poses: one image (height, width) with its (4, 4) camera-to-world pose, or
-    lists of both.  Every pixel with a finite positive depth is one ray from its camera's centre (backproject_depth: the convention of
-    pixel_rays and render).  weights: None, or an image per frame.  The result of refine_poses plus `pixel` (the flat row-major pixel index
-    of every ray) and `frame` (the index of its image)."""
+def _depth_rays(depth, K, t_world_cam, weights):
+    """z-depth images of pinhole cameras at known poses -> world-frame rays: (pts, origins, weights or None, pixel, frame)"""
     def images(x):
         return list(x) if isinstance(x, (list, tuple)) or np.asarray(x).ndim == 3 else [x]
     frames, cams = images(depth), images(t_world_cam)
     wimgs = [None] * len(frames) if weights is None else images(weights)
     if len(cams) != len(frames) or len(wimgs) != len(frames):
-        raise ValueError("refine_poses_depth: one pose (and one weight image) per depth image")
+        raise ValueError("one pose (and one weight image) per depth image")
     pts, org, w, pixel, frame = [], [], [], [], []
     for f, (img, cam, wimg) in enumerate(zip(frames, cams, wimgs)):
         p_cam, keep = backproject_depth(img, K)
@@ -190,10 +187,48 @@ def refine_poses_depth(engine, objects, depth, K, t_world_cam, weights=None, onl
         frame.append(np.full(keep.size, f, np.int64))
         if wimg is not None:
             w.append(np.asarray(wimg, np.float32).reshape(-1)[keep])
-    res, moved = refine_poses(engine, objects, np.concatenate(pts), np.concatenate(org), weights=np.concatenate(w) if w else None, only=only, trace=trace,
-                              **params)
-    res["pixel"], res["frame"] = np.concatenate(pixel), np.concatenate(frame)
+    return np.concatenate(pts), np.concatenate(org), np.concatenate(w) if w else None, np.concatenate(pixel), np.concatenate(frame)
+
+
+def refine_poses_depth(engine, objects, depth, K, t_world_cam, weights=None, only=None, trace=False, **params):
+    """refine_poses on z-depth images of pinhole cameras at KNOWN poses: one image (height, width) with its (4, 4) camera-to-world pose, or
+    lists of both.  Every pixel with a finite positive depth is one ray from its camera's centre (backproject_depth: the convention of
+    pixel_rays and render).  weights: None, or an image per frame.  The result of refine_poses plus `pixel` (the flat row-major pixel index
+    of every ray) and `frame` (the index of its image)."""
+    pts, org, w, pixel, frame = _depth_rays(depth, K, t_world_cam, weights)
+    res, moved = refine_poses(engine, objects, pts, org, weights=w, only=only, trace=trace, **params)
+    res["pixel"], res["frame"] = pixel, frame
     return res, moved
+
+
+def refine_shapes(engine, objects, pts_world, origins_world, weights=None, only=None, trace=False, **params):
+    """Engine.align_shapes_to_rays on the list read_map_objects returns: the sensor poses are known, the objects' SHAPE CODES -- and with
+    unknowns="pose+code" their poses -- are refitted to the world-frame depth rays, inside the map (occlusion, a ray charged only to the
+    object it sees).  Arguments and result as refine_poses; the new object list carries the returned codes and poses.  params: unknowns,
+    code_reg, code_anchor, code_tol, max_gap, raycast={...} and the fields of Engine.align_params."""
+    objects = list(objects)
+    poses = np.stack([np.asarray(o["pose"], np.float64) for o in objects]) if objects else np.zeros((0, 4, 4))
+    refine = None
+    if only is not None:
+        ids = [int(o["id"]) for o in objects]
+        missing = [int(i) for i in only if int(i) not in ids]
+        if missing:
+            raise ValueError("refine_shapes: no object with id %s in the map" % missing)
+        refine = np.array([i in {int(x) for x in only} for i in ids], np.uint8)
+    res = engine.align_shapes_to_rays(poses, [o["code"] for o in objects], pts_world, origins_world, weights=weights, refine=refine, trace=trace,
+                                      per_ray=True, **params)
+    new = [dict(o, pose=np.asarray(t, np.float64).copy(), code=np.asarray(c, np.float32)[:np.asarray(o["code"]).reshape(-1).shape[0]].copy())
+           for o, t, c in zip(objects, res["t_world_obj"], res["codes"])]
+    return with_ids(res, [o["id"] for o in objects]), new
+
+
+def refine_shapes_depth(engine, objects, depth, K, t_world_cam, weights=None, only=None, trace=False, **params):
+    """refine_shapes on z-depth images of pinhole cameras at KNOWN poses, as refine_poses_depth: the result of refine_shapes plus `pixel`
+    and `frame`."""
+    pts, org, w, pixel, frame = _depth_rays(depth, K, t_world_cam, weights)
+    res, new = refine_shapes(engine, objects, pts, org, weights=w, only=only, trace=trace, **params)
+    res["pixel"], res["frame"] = pixel, frame
+    return res, new
 
 
 def with_ids(result, ids):

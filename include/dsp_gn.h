@@ -541,8 +541,8 @@ int dsp_debug_align_rays_check(const dsp_align_params* params, const dsp_raycast
  * dsp_map_query refuses; params dsp_map_align refuses; a raycast dsp_map_raycast refuses; max_gap < max_dist or NaN; NULL origins with
  * n_rays > 0; a negative or non-finite weight; n_rays > 2^31 - 1; n_obj x ceil(n_rays / 64) pair counts or the objects' code biases beyond
  * dsp_map_raycast's budgets.
- * Out of scope: scale or code refinement; a world-axis mask on the degrees of freedom (yaw only); a prior on the correction; the conversion
- * of H into an edge of dsp_pg_edge_information. */
+ * Code refinement is dsp_map_align_shapes, below.  Out of scope: scale; a world-axis mask on the degrees of freedom (yaw only); a prior on
+ * the correction; the conversion of H into an edge of dsp_pg_edge_information. */
 int dsp_map_align_objects(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, const float* origins_world,
                           const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params* params,
                           const dsp_raycast_params* raycast, double max_gap, float* t_world_obj_out, double* correction, double* record, int32_t* obj,
@@ -560,6 +560,66 @@ int dsp_debug_align_objects_rows(int64_t n, const float* pts_world, const int32_
 int dsp_debug_align_objects_compose(int64_t n, const double* correction, const float* t_world_obj, float* t_world_obj_out);
 int dsp_debug_align_objects_check(const dsp_align_params* params, const dsp_raycast_params* raycast, double max_gap, const float* origins_world,
                                   const float* weights, int64_t n_rays, int64_t n_obj);
+
+/* ---- shape refinement: what SHAPE do the objects have, given depth rays from known sensor poses?  One 70-dim system per map object ----
+ * dsp_map_align_objects moves the map's objects; dsp_map_align_shapes refits their shape codes -- and, if asked, their poses with them --
+ * against the same world-frame depth rays, inside the map: one cast with occlusion between the objects, a ray charged only to the object
+ * it sees.  Observations, weights, refine, the cast, gradient, residual d, the max_gap match and the owner rule are
+ * dsp_map_align_objects' verbatim.  Unknowns per object: x = [v 3, omega 3, dz 64] (DSP_SHAPES_DIM); the pose part is
+ * dsp_map_align_objects' C_k <- exp(xi) C_k, the code part is additive on an fp64 code z_k that starts at the input code and is rounded
+ * ONCE to fp32 for every evaluation, where the object's code bias is recomputed from it.  Jacobian row of a used ray:
+ * J = [-g_w, -(p_w x g_w), s dsdf/dcode] with the code derivatives of the winner's jacobian row at the hit sample and the winner's scale
+ * s (one fp32 multiply): the dependence of t_hit and g_w on the code is dropped, the first-order treatment the pose part has too.
+ * H = sum w wh J J^T (70 x 70), b = -sum w wh J d, cost, sum of valid weights W and used count as dsp_map_align's.  The sums of an object
+ * run over its winners in ascending ray order, in blocks of 128 list positions, rows added one at a time in ascending order, blocks in
+ * ascending order (csrc/align_shapes_math.h): the same bits whatever the passes, chunks or grid; no float atomics.
+ * Step, host fp64, on the MEAN system A = H / W, g = b / W:  A_cc += code_reg + code_anchor and g_c -= code_reg z_c + code_anchor (z_c -
+ * z0_c) on the code entries (z0: the input code), A_ii += damp + lambda on all 70, then the entries that are not asked for (`unknowns`)
+ * and the code entries beyond a 32-D decoder's length are pinned (dx exactly 0), then a 70-dim Cholesky.  The cost that step control
+ * decides on, and that the record reports, is F = sum cost / W + code_reg |z|^2 + code_anchor |z - z0|^2.  code_reg is the reference
+ * optimiser's code regulariser; with few views most code directions are unobserved and damp (default 1e-4 here, on the mean system) is
+ * what conditions them.  Loop, statuses, min_points, step control: dsp_map_align_objects'; an object converges when max |v| < trans_tol,
+ * max |omega| < rot_tol and max |dz| < code_tol (strict).  A trial code or code bias that is not finite, or a trial pose the map's
+ * inversion refuses, ends the object with DSP_ALIGN_SINGULAR at its accepted state.
+ * Outputs: t_world_obj_out and correction as dsp_map_align_objects'; codes_out n_obj x 64 floats; record n_obj x DSP_SHAPES_RECORD doubles
+ * {dsp_map_align's first 8, H 70 x 70 (raw sums, undamped, full), b 70}; the per-ray four from one extra evaluation of the returned map;
+ * trace optional, n_obj x iterations x DSP_SHAPES_TRACE doubles {C_k evaluated 16, code evaluated 64 (fp64), decision, cost, lambda, used
+ * rays, dx solved 70}.  An object that is not refined or never stepped returns its input pose and code bytes; with unknowns ==
+ * DSP_SHAPES_POSE every code returns its input bytes; with unknowns == DSP_SHAPES_CODE every pose returns its input bytes and every
+ * correction is the identity.  DSP_E_ARG: everything dsp_map_align_objects refuses; unknowns 0 or with unknown bits; code_reg,
+ * code_anchor or code_tol negative or not finite.
+ * Out of scope: scale (Sim(3)); coupling between objects beyond occlusion; a prior from dsp_batch_posterior records; the 16-bit decoders. */
+#define DSP_SHAPES_CODE 1
+#define DSP_SHAPES_POSE 2
+#define DSP_SHAPES_DIM 70
+#define DSP_SHAPES_RECORD (8 + 70 * 70 + 70)
+#define DSP_SHAPES_TRACE (16 + 64 + 4 + 70)
+typedef struct dsp_shapes_params {
+    int32_t unknowns;                        /* DSP_SHAPES_CODE, DSP_SHAPES_POSE or both */
+    double code_reg, code_anchor, code_tol;  /* >= 0, finite */
+} dsp_shapes_params;
+/* dsp_align_params_default's values but damp 1e-4 (on the mean system); code only, code_reg 0, code_anchor 0, code_tol 1e-6.  Either may
+ * be NULL. */
+void dsp_shapes_params_default(dsp_align_params* params, dsp_shapes_params* shapes);
+int dsp_map_align_shapes(dsp_handle* h, const float* t_world_obj, const float* codes, int64_t n_obj, const float* pts_world, const float* origins_world,
+                         const float* weights, int64_t n_rays, const unsigned char* refine, const dsp_align_params* params,
+                         const dsp_shapes_params* shapes, const dsp_raycast_params* raycast, double max_gap, float* t_world_obj_out, float* codes_out,
+                         double* correction, double* record, int32_t* obj, float* dist, float* t_hit, int32_t* status, double* trace);
+/* Counts of the last dsp_map_align_shapes on this handle, laid out as dsp_map_align_objects_last_stats'. */
+int dsp_map_align_shapes_last_stats(dsp_handle* h, int64_t* counts7);
+/* Host only, no handle: csrc/align_shapes_math.h on arrays.  dsp_debug_align_shapes_rows: dsp_debug_align_objects_rows' inputs and gcode
+ * (n x 64: s dsdf/dcode per ray) -> sums, n_obj x 2558 {H 2485 (pairs i <= j, row-major), b 70, cost, sum of valid weights, used rays}.
+ * dsp_debug_align_shapes_step: H (70 x 70 raw sums, the upper triangle is read), b, W, the fp64 code z (64), the fp32 input code z0 (64),
+ * the decoder's code length (1 .. 64), shapes, damp, lambda and C (16) -> status (DSP_ALIGN_OK or DSP_ALIGN_SINGULAR), dx (70), C_trial
+ * (16) and z_trial (64 doubles); all three untouched when singular.  dsp_debug_align_shapes_check: DSP_E_ARG for what
+ * dsp_map_align_shapes refuses before it touches the device, the map's poses and codes excepted. */
+int dsp_debug_align_shapes_rows(int64_t n, const float* pts_world, const int32_t* winner, const int32_t* obj_row, const float* d, const float* grad_world,
+                                const float* gcode, const float* weights, int64_t n_obj, double huber, double max_dist, double* sums);
+int dsp_debug_align_shapes_step(const double* H4900, const double* b70, double W, const double* code, const float* code0, int32_t code_len,
+                                const dsp_shapes_params* shapes, double damp, double lambda, const double* c16, int32_t* status, double* dx70,
+                                double* c_trial16, double* code_trial64);
+int dsp_debug_align_shapes_check(const dsp_align_params* params, const dsp_shapes_params* shapes, const dsp_raycast_params* raycast, double max_gap,
+                                 const float* origins_world, const float* weights, int64_t n_rays, int64_t n_obj);
 
 /* ---- device-resident batches (bench / steady-state serving: inputs stay in HBM between runs) --- */
 int dsp_batch_create(dsp_handle* h, const dsp_gn_params* prm, int32_t n_objects, const int64_t* pts_off,
